@@ -6,20 +6,28 @@ one rank per GPU).  A "step" is one pass of the hot path (ONE fused kernel launc
 of synthetic input that is already resident in HBM: BASELINE.json configs[1] -- ETS Panda, 22 ETs,
 q ~ U(-pi,pi)^7, N = 1e6 per GPU, fp64.  W untimed warm-up steps, then exactly K timed steps between
 barrier+synchronize pairs; the MAX over ranks is the step time; rank 0 prints ONE JSON line.
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the line.  Everything
+else the benchmark measures or checks runs only with --full, after the timed steps (marked [--full] below).
+
+--dump-outputs DIR  after the timed steps, what the last step computed -- the arrays a caller of the timed path receives:
+               T (N,4,4) and J0 (N,6,7), or TJ (N,58) with --layout packed -- as DIR/<name>.npy, float64, on the
+               rows of a fixed seeded sample of 65536 rows (every row when N is no larger; split between the ranks,
+               whose files other than rank 0's carry a _rank<r> suffix).  The inputs depend only on the arguments.
 
 Extra objects on the line:
   roofline     achieved = 520 B/config x N / (average duration of the dominant kernel = the device-side duration
                of the K timed launches, ONE HIP-event pair on the launch stream around the timed loop, / K)
                against the 8 TB/s HBM3E peak; traffic = HBM bytes per launch from the committed rocprofv3 --pmc
                passes of this command (profiles/r06_pmc.json; `traffic_source` says so -- it is not measured
-               by this run), else null.
-  host_path    (N=1 only, never `value`) the same 1e6 configurations handed over as NumPy arrays through the
+               by this run), else null.  [--full] per_launch_event_min_ms, rotating_outputs, layouts, stream_probe.
+  host_path    [--full] (N=1 only, never `value`) the same 1e6 configurations handed over as NumPy arrays through the
                RTBHIP_MEM_HOST boundary: PCIe-inclusive configurations/s of the pinned, chunked, double-buffered
                H2D -> kernel -> D2H pipeline inside the library.
-  cpu_baseline the reference's OWN native code (oracle/_ref, built unmodified from the reference
+  cpu_baseline [--full] the reference's OWN native code (oracle/_ref, built unmodified from the reference
                sources) timed on this box's host cores on the same q array: one ETS_fkine call over
                the whole array + the Python per-row ETS_jacob0 loop a reference user needs today
                (kind "reference"); falls back to the plain-C restatement (kind "port").
+  secondary    [--full] BASELINE configs[2], [3], [4] with their in-run parity (benchsecondary.py).
 Multi-GPU: the batch dimension is embarrassingly parallel -> each rank owns N rows (weak scaling),
 no collective on the data path; the single output gather (RCCL all_gather over xGMI) is timed
 separately and reported as gather_ms, never inside `value`.  `--gpus N` with no launcher (WORLD_SIZE unset)
@@ -41,6 +49,21 @@ BYTES_PER_CONFIG = 56 + 128 + 336  # q read + T written + J0 written
 KERNEL = {"packed": "k_kin_reg<7,true,true,true> (rtbhip_fkine_jacob_packed: [T | J0] rows of one (N,58) array)",
           "two": "k_kin_reg<7,true,true,false> (rtbhip_fkine_jacob: T (N,4,4) and J0 (N,6,7))"}
 KERNEL_SUBSTR = {"packed": "k_kin_reg<7, true, true, true>", "two": "k_kin_reg<7, true, true, false>"}
+DUMP_ROWS = 65536                  # rows of the --dump-outputs sample: 65536 x (16 + 42) x 8 B = 30 MB
+
+
+def dump_outputs(out_dir, outs, layout, N, rank, world):
+    """--dump-outputs: the last timed step's output arrays, on a fixed sample of rows (seeded, sorted; every row when N is no larger),
+    as float64 .npy files -- the same files from run to run and from build to build for the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    k = max(1, DUMP_ROWS // world)
+    rows = np.arange(N) if N <= k else np.sort(np.random.default_rng(2024).choice(N, k, replace=False))
+    idx = torch.from_numpy(rows).to(outs[0].device)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    for name, a in zip(("TJ",) if layout == "packed" else ("T", "J0"), outs):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a.index_select(0, idx).cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline_all_cores(sample, timeout_s=90.0):
@@ -131,13 +154,17 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--n", type=int, default=1000000, help="configurations per GPU per step")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline and host_path legs")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` object (BASELINE configs[2], [3], [4] with their in-run parity)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything else the benchmark measures or checks: cpu_baseline, host_path, "
+                                                        "secondary, and the roofline's per-launch, rotating-output, layout and stream-probe figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a fixed sample of its output rows, float64) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline and host_path legs")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the `secondary` object (BASELINE configs[2], [3], [4] with their in-run parity)")
     ap.add_argument("--tune", action="append", default=[], help="key=value for rtbhip_tune (A/B runs)")
     ap.add_argument("--layout", choices=("packed", "two"), default="two",
                     help="output layout of the timed step: 'packed' = rtbhip_fkine_jacob_packed, one (N,58) array of [T | J0] rows (a single write "
                          "stream; the T||J gather message of SURVEY 8e); 'two' = rtbhip_fkine_jacob, T (N,4,4) and J0 (N,6,7) as two arrays.  Same "
-                         "arithmetic, same 520 algorithmic bytes per configuration, bit-identical values (the other layout is timed beside it)")
+                         "arithmetic, same 520 algorithmic bytes per configuration, bit-identical values (with --full the other layout is timed beside it)")
     ap.add_argument("--gather", action="store_true", help="build the process group and time the output gather even with one rank "
                                                           "(a world-size-1 RCCL group: rehearses the collective on a single-GPU box)")
     argv = bench_argv()
@@ -201,9 +228,11 @@ def main():
         TJ = None
 
     elapsed, kern_avg_ms = rk.timed_steps(step, args.steps, args.warmup)
-    kern_min_ms = per_launch_min_ms(step, min(args.steps, 50))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, args.layout, N, rank, world)
+    kern_min_ms = per_launch_min_ms(step, min(args.steps, 50)) if args.full else None
     rotating, layouts = None, None
-    if rank == 0 and world == 1 and not args.no_secondary:      # (--no-secondary: the profiling runs, whose kernel averages are of the timed loop alone)
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:      # (--no-secondary: the profiling runs, whose kernel averages are of the timed loop alone)
         # The timed loop above rewrites ONE output buffer set, as a control loop with preallocated outputs does.  Beside it, for BOTH layouts:
         # the sustained rate on one buffer set, and on THREE sets used in rotation -- every launch writes memory the previous two did not touch,
         # the rate at which results stream into memory that has to take them.  The two-array form's rate depends on where the allocator put
@@ -234,7 +263,7 @@ def main():
                     "what": "the timed layout (%s) under sustained timing: three output sets in rotation / one set" % args.layout}
         torch.cuda.empty_cache()
     probe = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # what the memory system of THIS box delivers for the same traffic (56 B read + 464 B written per configuration) through a plain
         # streaming kernel, measured the same way (events around 20 launches): the spread between boxes is 15-20 %, the data-sheet peak is not
         dst = torch.empty((N, 58), dtype=torch.float64, device=dev)
@@ -291,12 +320,14 @@ def main():
                        "backend": rk.backend if rk.dist is not None else None},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": KERNEL[args.layout], "layout": args.layout, "kernel_avg_ms": kern_avg_ms, "per_launch_event_min_ms": kern_min_ms,
-                         "kernel_avg_source": "one HIP-event pair on the launch stream around the K timed launches / K "
-                                              "(per_launch_event_min_ms: smallest of per-launch event pairs, each of which adds a few microseconds "
-                                              "-- it can exceed the loop average)",
+                         "kernel": KERNEL[args.layout], "layout": args.layout, "kernel_avg_ms": kern_avg_ms,
+                         "kernel_avg_source": "one HIP-event pair on the launch stream around the K timed launches / K",
                          "algorithmic_bytes_per_launch": BYTES_PER_CONFIG * N},
         }
+        if kern_min_ms is not None:
+            line["roofline"]["per_launch_event_min_ms"] = kern_min_ms
+            line["roofline"]["kernel_avg_source"] += (" (per_launch_event_min_ms: smallest of per-launch event pairs, each of which adds a few "
+                                                      "microseconds -- it can exceed the loop average)")
         committed = rocprof_committed(ROOT, KERNEL_SUBSTR[args.layout])
         if committed is not None:
             # the rocprofv3 --kernel-trace --stats figure of the SAME command committed under profiles/ (another lease, possibly another box:
@@ -365,10 +396,10 @@ def main():
                 ("RCCL through rtbhip_shard_gather, a world-size-1 communicator on one GPU (--gather: rehearsal of the collective, no xGMI traffic)" if world == 1
                  else "RCCL over xGMI through rtbhip_shard_gather")
                 if rk.backend == "nccl" else "gloo through host memory (test hook)")
-        if not args.no_cpu and world == 1:  # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu and world == 1:  # reported on rank 0 at N=1 only
             line["cpu_baseline"] = cpu_baseline(q_host, T, J)
             line["host_path"] = host_path(ets, q_host, T, J)
-        if not args.no_secondary and world == 1 and not rk.forced:
+        if args.full and not args.no_secondary and world == 1 and not rk.forced:
             # BASELINE configs[2], [3], [4] -- IK over 1e5 targets, RNE over 1e7 triples (and the 1.25e6 share), the 16-arm fleet -- each with
             # its HIP-event kernel time, an in-run parity figure against the reference's compiled code on a sample, and its roofline;
             # after the timed region, never inside `value` (benchsecondary.py)

@@ -4,9 +4,9 @@
 # Stages (any subset, run in this order; results under gpurun_out/$VISIT):
 #   tests   the whole `pytest -m gpu` suite WITHOUT -x (TESTS="path::id ..." narrows it)       -> pytest_gpu.log
 #   smoke   __graft_entry__.smoke()
-#   bench   python bench.py $BENCH_ARGS (default --steps 50 --warmup 5)                         -> bench_n1.json
+#   bench   python bench.py $BENCH_ARGS (default --steps 50 --warmup 5 --full)                  -> bench_n1.json
 #   prof    rocprofv3 --kernel-trace --stats of bench.py (and of the rne leg at 1e7)            -> prof/, prof_rne1e7/
-#   profsec rocprofv3 --kernel-trace --stats of the FULL bench.py command (secondary legs included); per (kernel, grid) durations    -> secondary_kernel_stats.csv
+#   profsec rocprofv3 --kernel-trace --stats of bench.py --full (secondary legs included); per (kernel, grid) durations    -> secondary_kernel_stats.csv
 #   pmc     FETCH_SIZE / WRITE_SIZE passes (separate runs) of bench.py and of the rne leg       -> pmc_*/
 #   sq      SQ_INSTS_VALU / SQ_WAVES of bench_extra.py --what $SQ_WHAT (default rne,dyn,tree)        -> pmc_sq/, sq_digest.txt
 #   extra   python bench_extra.py $EXTRA_ARGS                                                   -> bench_extra.jsonl
@@ -29,7 +29,7 @@ if has tests; then
 fi
 if has smoke; then timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1; fi
 if has bench; then
-  timeout 600 python bench.py ${BENCH_ARGS:---steps 50 --warmup 5} > $O/bench_n1.json 2> $O/bench_n1.err; cut -c1-300 $O/bench_n1.json; tail -3 $O/bench_n1.err
+  timeout 600 python bench.py ${BENCH_ARGS:---steps 50 --warmup 5 --full} > $O/bench_n1.json 2> $O/bench_n1.err; cut -c1-300 $O/bench_n1.json; tail -3 $O/bench_n1.err
   python scripts/bench_digest.py $O/bench_n1.json
 fi
 if has layout; then
@@ -48,7 +48,7 @@ if has prof; then
 fi
 if has profsec; then
   cd /tmp
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_secondary -o sec -- python $R/bench.py --steps 20 --warmup 3 --no-cpu > $O/prof_secondary.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_secondary -o sec -- python $R/bench.py --steps 20 --warmup 3 --no-cpu --full > $O/prof_secondary.log 2>&1
   cd $R
   python scripts/secondary_stats.py $O/prof_secondary $O/secondary_kernel_stats.csv | cut -c1-170
   tail -1 $O/prof_secondary.log | cut -c1-300

@@ -15,6 +15,8 @@ Run in the BUILD container (needs /root/reference and oracle/_ref built by
                             is involved even across many searches), and of `fknm.Angle_Axis` on random, identical,
                             half-turn and near-threshold rotation pairs.  `python make_golden.py python_ik` writes
                             only this file.
+  reference_function_tables.json : the method tables of the reference's fknm / frne extension modules (names only);
+                            `python make_golden.py function_tables` writes only this file.
 """
 import ast
 import json
@@ -175,10 +177,25 @@ def xacro_golden():
     print("wrote", dst, len(out), "bytes")
 
 
+def function_tables():
+    """tests/golden/reference_function_tables.json: the method names of the reference's extension modules, in table order
+    (core/fknm.cpp and core/frne.c, the PyMethodDef arrays) -- what rtbhip.compat.fknm / .frne must export."""
+    import re
+    core = os.path.join(REF_ROOT, "src", "roboticstoolbox", "core")
+    tables = {"fknm": re.findall(r'\{"(\w+)",\s*\(PyCFunction\)', open(os.path.join(core, "fknm.cpp")).read()),
+              "frne": re.findall(r'"(\w+)",\s*\(PyCFunction\)', open(os.path.join(core, "frne.c")).read())}
+    with open(os.path.join(HERE, "reference_function_tables.json"), "w") as f:
+        json.dump(tables, f, indent=1)
+        f.write("\n")
+    print("wrote reference_function_tables.json:", {k: len(v) for k, v in tables.items()})
+
+
 def main():
     if sys.argv[1:] == ["xacro"]:
         xacro_golden()
         return
+    if sys.argv[1:] == ["function_tables"]:
+        return function_tables()
     if sys.argv[1:] == ["python_ik"]:
         return python_ik()
     lit = {}

@@ -7,8 +7,8 @@
                 is present, with the reference-run fixtures otherwise.
 """
 import contextlib
+import json
 import os
-import re
 
 import numpy as np
 import numpy.testing as nt
@@ -42,12 +42,11 @@ def test_shim_exports_the_reference_function_tables():
         assert callable(getattr(compat.fknm, n)), n
     for n in FRNE_NAMES:
         assert callable(getattr(compat.frne, n)), n
-    src = "/root/reference/src/roboticstoolbox/core/fknm.cpp"
-    if os.path.exists(src):                                   # build container: the list above IS the reference's table
-        table = re.findall(r'\{"(\w+)",\s*\(PyCFunction\)', open(src).read())
-        assert sorted(set(table) - {"r2q"}) == sorted(FKNM_NAMES)
-        table = re.findall(r'"(\w+)",\s*\(PyCFunction\)', open(src.replace("fknm.cpp", "frne.c")).read())
-        assert sorted(table) == sorted(FRNE_NAMES)
+    # the lists above ARE the reference's method tables (tests/golden/reference_function_tables.json, make_golden.py function_tables)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_function_tables.json")) as f:
+        tables = json.load(f)
+    assert sorted(set(tables["fknm"]) - {"r2q"}) == sorted(FKNM_NAMES)
+    assert sorted(tables["frne"]) == sorted(FRNE_NAMES)
 
 
 def test_install_and_opt_in_switch(monkeypatch):

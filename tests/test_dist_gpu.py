@@ -265,12 +265,12 @@ def test_bench_gpus_8_on_a_smaller_box_fails_with_one_clear_line():
 
 
 def test_bench_single_gpu_line_carries_the_contract_objects():
-    """`python bench.py` as the driver runs it (N = 1, default workload): ONE JSON line with the contract's keys, the roofline
+    """`python bench.py --full` (N = 1, default workload): ONE JSON line with the contract's keys, the roofline
     object priced on 520 B per configuration, the reference-built CPU baseline, and the host-pointer rate as its own object."""
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RTBHIP_BENCH_BACKEND"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3"], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--full"], capture_output=True, text=True,
                        timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -309,3 +309,36 @@ def test_bench_single_gpu_line_carries_the_contract_objects():
     assert fleet["chains"] == 17 and fleet["arms"]["YuMi"] == 14 and min(fleet["arms"].values()) == 4 and max(fleet["arms"].values()) == 14
     assert fleet["parity"]["max_abs_err_yumi_arms"] <= 1e-10 and fleet["packed_layout_ms"] > 0 and fleet["packed_rows_equal_two_arrays"] is True
     assert fleet["sixteen_chain_form"]["kernel_avg_ms"] > 0 and 0.0 < fleet["sixteen_chain_form"]["roofline"]["frac"] < 1.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_the_timed_step_computed(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the contract line and nothing the headline does not need, and the
+    last timed step's T and J0 on the fixed row sample, equal to the CPU oracle's on the same (seed 0) inputs -- and the same files on a second run."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RTBHIP_BENCH_BACKEND", "RTBHIP_BENCH_FORCE_GROUP"):
+        env.pop(k, None)
+    N = 200000
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--n", str(N), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["value"] == pytest.approx(N / (line["ms_per_step"] * 1e-3), rel=1e-9)
+        for k in ("cpu_baseline", "host_path", "secondary"):
+            assert k not in line, k
+        for k in ("rotating_outputs", "layouts", "stream_probe", "per_launch_event_min_ms"):
+            assert k not in line["roofline"], k
+        assert sorted(os.listdir(d)) == ["J0.npy", "T.npy"]
+        dumps.append((np.load(d / "T.npy"), np.load(d / "J0.npy")))
+    (T, J), (T2, J2) = dumps
+    assert T.dtype == np.float64 and T.shape == (65536, 4, 4) and J.shape == (65536, 6, 7)
+    assert np.array_equal(T, T2) and np.array_equal(J, J2)
+    from oracle import oracle, chains
+    rows = np.sort(np.random.default_rng(2024).choice(N, 65536, replace=False))
+    q = np.random.default_rng(0).uniform(-np.pi, np.pi, (N, 7))[rows]
+    ch = chains.panda_ets()
+    assert np.abs(T - oracle.fkine(ch, q)).max() <= 1e-10 and np.abs(J - oracle.jacob0(ch, q)).max() <= 1e-10
