@@ -128,6 +128,18 @@ int rtbhip_fkine_jacob(rtbhip_chain_t chain, const double *q, int64_t N, const d
 int rtbhip_fkine_jacob_packed(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16,
                               const double *tool16, int32_t frame, double *TJ, int32_t mem, void *stream);
 
+/* FLOAT32 ROWS.  rtbhip_fkine_jacob / rtbhip_fkine_jacob_packed with q, T, J and TJ held as float in device memory (a float32 torch tensor):
+ * same arguments, same shapes, same kernels' arithmetic -- a q is widened to double after its load, the chain walk is the fp64 one, and a
+ * result is rounded to float once (round to nearest even) before its store, so the output equals (float) of the fp64 entry's output on
+ * (double) q, bit for bit.  Half the bytes per configuration (260 instead of 520 for a 7-joint arm).  base16 / tool16 stay double (per-call
+ * constants).  T or J may be NULL (fkine alone / jacob0, jacobe alone), not both.  mem must be RTBHIP_MEM_DEVICE: RTBHIP_EINVAL for host
+ * pointers (a host array is converted by its owner; that path is bound by the host link).  Pointers need 4-byte alignment only. */
+int rtbhip_fkine_jacob_f32(rtbhip_chain_t chain, const float *q, int64_t N, const double *base16,
+                           const double *tool16, int32_t frame, float *T, float *J, int32_t mem,
+                           void *stream);
+int rtbhip_fkine_jacob_packed_f32(rtbhip_chain_t chain, const float *q, int64_t N, const double *base16,
+                                  const double *tool16, int32_t frame, float *TJ, int32_t mem, void *stream);
+
 /* ETS_hessian0 / ETS_hessiane (fknm.cpp:583-783 -> methods.cpp:16-32), batched: H is (N,n,6,n). */
 int rtbhip_hessian(rtbhip_chain_t chain, const double *q, int64_t N, const double *tool16,
                    int32_t frame, double *H, int32_t mem, void *stream);
@@ -266,6 +278,13 @@ int rtbhip_dyn_upload(rtbhip_dyn_t dyn, int32_t device); /* as rtbhip_chain_uplo
  * robot/Dynamics.py:863-922, and Dynamics.itorque, :1407-1465, feed the reference's rne). */
 int rtbhip_rne(rtbhip_dyn_t dyn, const double *q, const double *qd, const double *qdd, int64_t N,
                const double *grav3, const double *fext6, double *tau, int32_t mem, void *stream);
+
+/* rtbhip_rne with q, qd, qdd and tau held as float in device memory (see rtbhip_fkine_jacob_f32: fp64 arithmetic, one rounding per torque;
+ * grav3 / fext6 stay double; mem must be RTBHIP_MEM_DEVICE).  Served by the kernels built into the library -- the general ones and the
+ * Panda / Puma560 structure instantiations; a robot whose fp64 calls run a kernel compiled at run time gets its general kernel here, which
+ * returns the same numbers. */
+int rtbhip_rne_f32(rtbhip_dyn_t dyn, const float *q, const float *qd, const float *qdd, int64_t N,
+                   const double *grav3, const double *fext6, float *tau, int32_t mem, void *stream);
 
 /* DHRobot.rne(..., base_wrench=True) -> rne_python (robot/DHRobot.py:1409-1412, 1765-1770), batched: the torques as rtbhip_rne and
  * wbase (N,6) = [R_1 f_1, R_1 n_1], the force and moment the base exerts on link 1, rotated into frame 0 -- what the backward

@@ -371,6 +371,40 @@ static int kin_packed_entry(rtbhip_chain_t h, const double *q, int64_t N, const 
     });
 }
 
+
+// ---- float32 device rows (rtbhip_fkine_jacob_f32, rtbhip_fkine_jacob_packed_f32, rtbhip_rne_f32): the validation of the fp64 entries; host
+// pointers are refused -- the host path converts nothing and is bound by the PCIe link, not by the width of a row (hostpipe.cpp is fp64 only)
+static int check_f32_device(const char *fn, int mem)
+{
+    if (mem == RTBHIP_MEM_HOST) { set_error(std::string(fn) + ": float32 rows are served in device memory only (mem must be RTBHIP_MEM_DEVICE)"); return RTBHIP_EINVAL; }
+    return RTBHIP_OK;
+}
+
+static int kin_entry_f32(const char *fn, rtbhip_chain_t h, const float *q, int64_t N, const double *base16, const double *tool16, int frame,
+                         float *T, float *J, float *TJ, bool packed, int mem, void *stream)
+{
+    const std::shared_ptr<Chain> c_owner = chain_from_handle(h);
+    Chain *c = c_owner.get();
+    RTB_TRACE((std::string("rtbhip_") + fn).c_str());
+    if (!c) { set_error(std::string(fn) + ": unknown chain handle"); return RTBHIP_EINVAL; }
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    RTB_TRY(check_f32_device(fn, mem));
+    if (frame != 0 && frame != 1) { set_error(std::string(fn) + ": frame must be 0 (jacob0) or 1 (jacobe)"); return RTBHIP_EINVAL; }
+    if (N > 0 && !T && !J && !TJ) { set_error(std::string(fn) + ": no output buffer"); return RTBHIP_EINVAL; }
+    if (N == 0) return RTBHIP_OK;
+    if (c->n == 0) {                  // a chain of constants: J is (N, 6, 0), a packed row the pose alone (as the fp64 entries)
+        J = nullptr;
+        if (packed) { T = TJ; packed = false; }
+        if (!T) return RTBHIP_OK;
+    }
+    DevChain ops;
+    RTB_TRY(chain_device_ops(c, &ops, nullptr));
+    Affine base = affine_from16(base16), tool = affine_from16(tool16);
+    if (packed) return launch_kin_packed_f32(c, ops, q, N, base, tool, frame, TJ, (hipStream_t)stream);
+    return launch_kin_f32(c, ops, q, N, base, tool, frame, T, J, (hipStream_t)stream);
+}
+
 void kin_tune(const char *key, int value);
 void rne_tune(const char *key, int value);
 void ik_tune(const char *key, int value);
@@ -604,6 +638,20 @@ int rtbhip_fkine_jacob_packed(rtbhip_chain_t chain, const double *q, int64_t N, 
                               const double *tool16, int32_t frame, double *TJ, int32_t mem, void *stream)
 {
     return kin_packed_entry(chain, q, N, base16, tool16, frame, TJ, mem, stream);
+}
+
+int rtbhip_fkine_jacob_f32(rtbhip_chain_t chain, const float *q, int64_t N, const double *base16,
+                           const double *tool16, int32_t frame, float *T, float *J, int32_t mem,
+                           void *stream)
+{
+    return kin_entry_f32("fkine_jacob_f32", chain, q, N, base16, tool16, frame, T, J, nullptr, false, mem, stream);
+}
+
+int rtbhip_fkine_jacob_packed_f32(rtbhip_chain_t chain, const float *q, int64_t N, const double *base16,
+                                  const double *tool16, int32_t frame, float *TJ, int32_t mem, void *stream)
+{
+    if (N > 0 && !TJ) { set_error("fkine_jacob_packed_f32: no output buffer"); return RTBHIP_EINVAL; }
+    return kin_entry_f32("fkine_jacob_packed_f32", chain, q, N, base16, tool16, frame, nullptr, nullptr, TJ, true, mem, stream);
 }
 
 int rtbhip_hessian(rtbhip_chain_t chain, const double *q, int64_t N, const double *tool16,
@@ -1093,6 +1141,25 @@ int rtbhip_rne(rtbhip_dyn_t dyn, const double *q, const double *qd, const double
 {
     RTB_TRACE("rtbhip_rne");
     return rne_entry("rne", dyn, q, qd, qdd, N, grav3, fext6, tau, nullptr, false, mem, stream);
+}
+
+int rtbhip_rne_f32(rtbhip_dyn_t dyn, const float *q, const float *qd, const float *qdd, int64_t N,
+                   const double *grav3, const double *fext6, float *tau, int32_t mem, void *stream)
+{
+    RTB_TRACE("rtbhip_rne_f32");
+    const char *fn = "rne_f32";
+    const std::shared_ptr<Dyn> d_owner = dyn_from_handle(dyn);
+    Dyn *d = d_owner.get();
+    if (!d) { set_error(std::string(fn) + ": unknown dyn handle"); return RTBHIP_EINVAL; }
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    RTB_TRY(check_f32_device(fn, mem));
+    if (!grav3) { set_error(std::string(fn) + ": NULL gravity"); return RTBHIP_EINVAL; }
+    if (N > 0 && !tau) { set_error(std::string(fn) + ": NULL tau"); return RTBHIP_EINVAL; }   // qd / qdd may be NULL (= zeros)
+    if (N == 0) return RTBHIP_OK;
+    const DevLink *links = nullptr;
+    RTB_TRY(dyn_device_links(d, &links));
+    return launch_rne_f32(d, links, q, qd, qdd, N, grav3, fext6, tau, (hipStream_t)stream);
 }
 
 int rtbhip_rne_base_wrench(rtbhip_dyn_t dyn, const double *q, const double *qd, const double *qdd, int64_t N,

@@ -40,12 +40,11 @@ constexpr int kKinPosePlain = 1;      // KinParams.pad bit 0
 #endif
 constexpr int kKinPacked = 2;         // KinParams.pad bit 1: T is the packed (N, 16 + 6n) array [T | J], J is not written separately (run-time-n tile)
 
-template <bool WANT_T, bool WANT_J, bool WANT_H, bool COALESCED>
-__global__ __launch_bounds__(kWave) void k_kin(KinParams kp, DevChain dc,
-                                              const double *__restrict__ q, double *__restrict__ T,
-                                              double *__restrict__ J, double *__restrict__ H)
+// the run-time-n tile loop; S = storage type of q, T and J (kin_tile.h: double, or float for the _f32 entry points; H is fp64 only)
+template <bool WANT_T, bool WANT_J, bool WANT_H, bool COALESCED, class S>
+__device__ __forceinline__ void kin_tiles(KinParams kp, DevChain dc, const S *__restrict__ q, S *__restrict__ T, S *__restrict__ J,
+                                          double *__restrict__ H, double *lds)
 {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
     double *rows = lds;
     double *qs = lds + kWave * kp.stride;
     const ConstChain ops = const_view(dc);
@@ -96,14 +95,30 @@ __global__ __launch_bounds__(kWave) void k_kin(KinParams kp, DevChain dc,
     }
 }
 
+template <bool WANT_T, bool WANT_J, bool WANT_H, bool COALESCED>
+__global__ __launch_bounds__(kWave) void k_kin(KinParams kp, DevChain dc,
+                                              const double *__restrict__ q, double *__restrict__ T,
+                                              double *__restrict__ J, double *__restrict__ H)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    kin_tiles<WANT_T, WANT_J, WANT_H, COALESCED>(kp, dc, q, T, J, H, lds);
+}
+// float32 q, T, J (and packed [T | J] rows): the same tile loop, coalesced form
+template <bool WANT_T, bool WANT_J>
+__global__ __launch_bounds__(kWave) void k_kin_f32(KinParams kp, DevChain dc, const float *__restrict__ q, float *__restrict__ T, float *__restrict__ J)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    kin_tiles<WANT_T, WANT_J, false, true>(kp, dc, q, T, J, (double *)nullptr, lds);
+}
+
 // ---------------------------------------------------------------- register-resident variant (n <= 8)
 #ifndef RTB_REG_WAVES
 #define RTB_REG_WAVES 3   // waves per SIMD the register allocator must leave room for (<= 168 VGPRs)
 #endif
 // One register-resident tile (64 configurations) of a chain with NJ joints; shared by k_kin_reg and k_fleet.
-template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false>
-__device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &cv, const double *__restrict__ q,
-                                         double *__restrict__ T, double *__restrict__ J, double *buf, int lane,
+template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false, class S>
+__device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &cv, const S *__restrict__ q,
+                                         S *__restrict__ T, S *__restrict__ J, double *buf, int lane,
                                          int64_t tile)
 {
     constexpr int W = 6 * NJ;
@@ -167,6 +182,14 @@ __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints ? RTB_REG_WAVES : 2)) v
 {
     extern __shared__ __attribute__((aligned(16))) double buf[];
     // (the packed form writes ~30 KB runs per wave: like the Hessian tile it may prefer the identity mapping -- RTB_PACKED_XCD, A/B'd in profiles/r05_*)
+    reg_tile<NJ, WANT_T, WANT_J, PACKED>(kp, const_view(dc), q, T, J, buf, threadIdx.x, (PACKED && !RTB_PACKED_XCD) ? blockIdx.x : xcd_tile());
+}
+// float32 q, T, J (PACKED: [T | J] rows): the same tile, the same launch shape; only the widths of the row accesses differ (kin_tile.h)
+template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false>
+__global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints ? RTB_REG_WAVES : 2)) void k_kin_reg_f32(KinParams kp, DevChain dc, const float *__restrict__ q,
+                                                      float *__restrict__ T, float *__restrict__ J)
+{
+    extern __shared__ __attribute__((aligned(16))) double buf[];
     reg_tile<NJ, WANT_T, WANT_J, PACKED>(kp, const_view(dc), q, T, J, buf, threadIdx.x, (PACKED && !RTB_PACKED_XCD) ? blockIdx.x : xcd_tile());
 }
 
@@ -535,11 +558,19 @@ void kin_tune(const char *key, int value)
     if (k == "diff_sig") g_diff_sig = value != 0;
 }
 
-template <bool WT, bool WJ, bool WH>
+template <bool WT, bool WJ, bool WH, class S>
 static hipError_t launch_variant(bool coalesced, dim3 grid, size_t lds, hipStream_t s, const KinParams &kp,
-                                 const DevChain &ops, const double *q, double *T, double *J, double *H)
+                                 const DevChain &ops, const S *q, S *T, S *J, double *H)
 {
-    if (coalesced) {
+    if constexpr (sizeof(S) == 4) {
+        static_assert(!WH, "the Hessian is fp64 only");
+        auto k = k_kin_f32<WT, WJ>;
+        if (lds > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k, grid, dim3(kWave), lds, s, kp, ops, q, T, J);
+    } else if (coalesced) {
         auto k = k_kin<WT, WJ, WH, true>;
         if (lds > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -566,6 +597,15 @@ static hipError_t launch_reg(dim3 grid, size_t lds, hipStream_t s, const KinPara
     else hipLaunchKernelGGL((k_kin_reg<NJ, false, true>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
     return hipGetLastError();
 }
+template <int NJ>
+static hipError_t launch_reg(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc,
+                             const float *q, float *T, float *J)
+{
+    if (T && J) hipLaunchKernelGGL((k_kin_reg_f32<NJ, true, true>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
+    else if (T) hipLaunchKernelGGL((k_kin_reg_f32<NJ, true, false>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
+    else hipLaunchKernelGGL((k_kin_reg_f32<NJ, false, true>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
+    return hipGetLastError();
+}
 
 template <int NJ>
 static hipError_t launch_reg_packed(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const double *q, double *TJ)
@@ -573,10 +613,18 @@ static hipError_t launch_reg_packed(dim3 grid, size_t lds, hipStream_t s, const 
     hipLaunchKernelGGL((k_kin_reg<NJ, true, true, true>), grid, dim3(kWave), lds, s, kp, dc, q, TJ, (double *)nullptr);
     return hipGetLastError();
 }
+template <int NJ>
+static hipError_t launch_reg_packed(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const float *q, float *TJ)
+{
+    hipLaunchKernelGGL((k_kin_reg_f32<NJ, true, true, true>), grid, dim3(kWave), lds, s, kp, dc, q, TJ, (float *)nullptr);
+    return hipGetLastError();
+}
 
 // rtbhip_fkine_jacob_packed: rows [T (16, base applied) | J (6n)] of ONE (N, 16 + 6n) array -- a single write stream (SURVEY 8e's T||J message)
-int launch_kin_packed(const Chain *c, const DevChain &ops, const double *q, int64_t N, const Affine &base,
-                      const Affine &tool, int frame, double *TJ, hipStream_t s)
+// (S: the rows' storage type, as launch_kin_s below)
+template <class S>
+static int launch_kin_packed_s(const Chain *c, const DevChain &ops, const S *q, int64_t N, const Affine &base,
+                               const Affine &tool, int frame, S *TJ, hipStream_t s)
 {
     if (N == 0) return RTBHIP_OK;
     KinParams kp;
@@ -613,10 +661,25 @@ int launch_kin_packed(const Chain *c, const DevChain &ops, const double *q, int6
     if (e != hipSuccess) return hip_fail(e, "k_kin (packed) launch");
     return RTBHIP_OK;
 }
-
-int launch_kin(const Chain *c, const DevChain &ops, const double *q, int64_t N, const Affine &base,
-               const Affine &tool, int frame, double *T, double *J, double *H, hipStream_t s)
+int launch_kin_packed(const Chain *c, const DevChain &ops, const double *q, int64_t N, const Affine &base,
+                      const Affine &tool, int frame, double *TJ, hipStream_t s)
 {
+    return launch_kin_packed_s(c, ops, q, N, base, tool, frame, TJ, s);
+}
+int launch_kin_packed_f32(const Chain *c, const DevChain &ops, const float *q, int64_t N, const Affine &base,
+                          const Affine &tool, int frame, float *TJ, hipStream_t s)
+{
+    return launch_kin_packed_s(c, ops, q, N, base, tool, frame, TJ, s);
+}
+
+// S: the storage type of q, T and J -- double (every entry point of the fp64 ABI), or float (rtbhip_fkine_jacob_f32; H must then be NULL).  Same
+// dispatch for both: a joint count of 1..kKinRegMax takes the register-resident tile (k_kin_reg / k_kin_reg_f32), a longer chain the run-time-n
+// tile (k_kin / k_kin_f32), with the same grids and the same LDS requests -- the tiles are fp64 in both forms.
+template <class S>
+static int launch_kin_s(const Chain *c, const DevChain &ops, const S *q, int64_t N, const Affine &base,
+                        const Affine &tool, int frame, S *T, S *J, double *H, hipStream_t s)
+{
+    constexpr bool kF64 = sizeof(S) == 8;
     if (N == 0) return RTBHIP_OK;
     KinParams kp;
     kp.n = c->n;
@@ -624,7 +687,7 @@ int launch_kin(const Chain *c, const DevChain &ops, const double *q, int64_t N, 
     kp.stride = kin_stride(c->n);
     kp.frame = frame;
     kp.has_base = base.used;
-    kp.pad = (T && J && !H && (long long)N * 128 <= kPoseCacheBytes) ? kKinPosePlain : 0;      // (see the store policy at the top of this file)
+    kp.pad = (T && J && !H && (long long)N * 16 * (long long)sizeof(S) <= kPoseCacheBytes) ? kKinPosePlain : 0;      // (see the store policy at the top of this file)
     kp.N = N;
     for (int i = 0; i < 12; i++) kp.base[i] = base.v[i];
     chain_tail(c, tool, kp.tail);
@@ -632,6 +695,7 @@ int launch_kin(const Chain *c, const DevChain &ops, const double *q, int64_t N, 
     int64_t g = (tiles + g_tiles_per_wave - 1) / g_tiles_per_wave;
     if (g > 0x7fffffff) g = 0x7fffffff;
     dim3 grid((unsigned)g);
+    if constexpr (kF64) {
     if (g_use_reg && H && !T && !J && c->n >= 1 && c->n <= kKinRegMax && tiles <= 0x7fffffff) {
         grid = dim3((unsigned)tiles);
         hipError_t e = hipSuccess;
@@ -649,6 +713,7 @@ int launch_kin(const Chain *c, const DevChain &ops, const double *q, int64_t N, 
         }
         if (e != hipSuccess) return hip_fail(e, "k_kin_hess launch");
         return RTBHIP_OK;
+    }
     }
     if (g_use_reg && !H && c->n >= 1 && c->n <= kKinRegMax && tiles <= 0x7fffffff) {
         grid = dim3((unsigned)tiles);
@@ -679,12 +744,22 @@ int launch_kin(const Chain *c, const DevChain &ops, const double *q, int64_t N, 
     if (wt && wj && !wh) e = launch_variant<true, true, false>(co, grid, lds, s, kp, ops, q, T, J, H);
     else if (wt && !wj && !wh) e = launch_variant<true, false, false>(co, grid, lds, s, kp, ops, q, T, J, H);
     else if (!wt && wj && !wh) e = launch_variant<false, true, false>(co, grid, lds, s, kp, ops, q, T, J, H);
-    else if (!wt && !wj && wh) e = launch_variant<false, false, true>(co, grid, lds, s, kp, ops, q, T, J, H);
-    else if (wt && wj && wh) e = launch_variant<true, true, true>(co, grid, lds, s, kp, ops, q, T, J, H);
+    else if (kF64 && !wt && !wj && wh) { if constexpr (kF64) e = launch_variant<false, false, true>(co, grid, lds, s, kp, ops, q, T, J, H); }
+    else if (kF64 && wt && wj && wh) { if constexpr (kF64) e = launch_variant<true, true, true>(co, grid, lds, s, kp, ops, q, T, J, H); }
     else { set_error("launch_kin: unsupported output combination"); return RTBHIP_EINVAL; }
     note_launch((int)grid.x, kWave, (int)lds);
     if (e != hipSuccess) return hip_fail(e, "k_kin launch");
     return RTBHIP_OK;
+}
+int launch_kin(const Chain *c, const DevChain &ops, const double *q, int64_t N, const Affine &base,
+               const Affine &tool, int frame, double *T, double *J, double *H, hipStream_t s)
+{
+    return launch_kin_s(c, ops, q, N, base, tool, frame, T, J, H, s);
+}
+int launch_kin_f32(const Chain *c, const DevChain &ops, const float *q, int64_t N, const Affine &base,
+                   const Affine &tool, int frame, float *T, float *J, hipStream_t s)
+{
+    return launch_kin_s(c, ops, q, N, base, tool, frame, T, J, (double *)nullptr, s);
 }
 
 // ---------------------------------------------------------------- mixed fleet (BASELINE config 5)

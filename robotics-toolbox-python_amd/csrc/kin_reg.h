@@ -201,12 +201,14 @@ RTB_HD void reg_core(const CV &cv, TL tail /* tail[k], k = 0..11 */, int frame, 
 
 // whole per-lane compute of one tile: q row in memory -> (P, J)
 // SIG != 0: the chain's structure signature (all joints revolute, none flipped, no tool: the tail is segment NJ of the table) -- the straight-line walk
-template <int NJ, bool WANT_J, SegSig SIG = 0, class CV>
-RTB_HD void reg_compute(const KinParams &kp, const CV &cv, const double *__restrict__ q, int64_t cfg,
+// S: the storage type of q (kin_tile.h): a float row is read with the same per-lane accesses, half as wide -- the wave's 64 rows are one contiguous
+// run of 64 * 4 qw bytes whose lines the NJ loads of the wave consume whole between them -- and widened here; everything after is fp64
+template <int NJ, bool WANT_J, SegSig SIG = 0, class CV, class S>
+RTB_HD void reg_compute(const KinParams &kp, const CV &cv, const S *__restrict__ q, int64_t cfg,
                         Pose &P, double (&jac)[6 * NJ])
 {
     const bool live = cfg < kp.N;
-    const double *qrow = q + cfg * kp.qw;
+    const S *qrow = q + cfg * kp.qw;
     double qv[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) qv[j] = live ? qrow[jm_jq(cv.jmeta[j])] : 0.0;

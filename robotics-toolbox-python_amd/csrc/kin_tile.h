@@ -36,11 +36,12 @@ RTB_HD int kin_stride(int n)
 RTB_HD size_t kin_lds_bytes(int n, int qw) { return (size_t)kWave * (kin_stride(n) + qw) * sizeof(double); }
 
 // phase A: this lane's joint coordinates -> qs (zero for lanes past the end of the batch)
-RTB_HD void kin_load_q(const KinParams &kp, const double *__restrict__ q, int64_t cfg, int lane,
+template <class S>
+RTB_HD void kin_load_q(const KinParams &kp, const S *__restrict__ q, int64_t cfg, int lane,
                        double *qs)
 {
     const bool live = cfg < kp.N;
-    const double *src = q + cfg * kp.qw;
+    const S *src = q + cfg * kp.qw;
     int c = 0;
     for (; c + 4 <= kp.qw; c += 4) {  // 4 independent loads in flight before the first LDS write
         double a0 = live ? src[c] : 0.0, a1 = live ? src[c + 1] : 0.0;
@@ -81,11 +82,34 @@ RTB_HD void kin_stage_T(const KinParams &kp, int lane, double *rows, Pose P)
 #define RTB_NT_STORE 1
 #endif
 
+// STORAGE TYPE of the per-row arrays (q in; T, J, [T | J] out): double, or float for float32 tensors (rtbhip_fkine_jacob_f32 ...).  The arithmetic is
+// fp64 either way: a float is widened right after its load and a result is rounded once (round-to-nearest-even, the plain conversion) right
+// before its store, so a float32 call returns exactly float(fp64 call on the widened input).  The LDS tiles stay fp64 in both forms -- the
+// run-time-n walk keeps its (p_j, z_j) scratch there -- and a lane writes the same PAIR of staged values per instruction in both: 16 bytes of
+// doubles or 8 bytes of floats.  The LDS side of a flush (pair reads, odd row strides, the piece bookkeeping) is therefore the fp64 one, and a
+// float wave-instruction covers a contiguous 512-byte run = four whole 128-byte lines.  (Four floats per lane were weighed: the lanes of a
+// ds_read_b64 would then be 8 dwords apart, 4-way on the 64 banks instead of 2-way, for half the store instructions.)  A float pointer is only
+// assumed 4-byte aligned: an offset view of a float32 tensor is a legal argument.
+template <bool NT>
+RTB_HD void store_pair_f32(float *__restrict__ dst, double a, double b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    typedef v2f v2f_a4 __attribute__((aligned(4)));
+    v2f w = {(float)a, (float)b};
+    if (NT && RTB_NT_STORE) __builtin_nontemporal_store(w, reinterpret_cast<v2f_a4 *>(dst));   // global_store_dwordx2 ... nt
+    else *reinterpret_cast<v2f_a4 *>(dst) = w;
+#else
+    dst[0] = (float)a;
+    dst[1] = (float)b;
+#endif
+}
+
 // phases C / E: the wave writes `ncfg` staged rows of W doubles (W even) as one contiguous run.
 // Lane l writes the 16-byte pieces l, l+64, l+128, ... of the run; (cfg, e) tracks which staged
 // row / element piece f falls in without a division per piece.
-template <bool NT = true>
-RTB_HD void kin_flush(const double *rows, int stride, int W, int ncfg, double *__restrict__ dst,
+template <bool NT = true, class S>
+RTB_HD void kin_flush(const double *rows, int stride, int W, int ncfg, S *__restrict__ dst,
                       int lane)
 {
     const int total = ncfg * W;
@@ -94,6 +118,13 @@ RTB_HD void kin_flush(const double *rows, int stride, int W, int ncfg, double *_
     const int da = 128 / W, db = 128 - da * W;
     for (; f < total; f += 128) {
         const double *src = rows + cfg * stride + e;
+        if constexpr (sizeof(S) == 4) {
+            store_pair_f32<NT>(dst + f, src[0], src[1]);
+            e += db;
+            cfg += da;
+            if (e >= W) { e -= W; cfg += 1; }
+            continue;
+        }
         double2 v;
         v.x = src[0];
         v.y = src[1];
@@ -117,8 +148,8 @@ RTB_HD void kin_flush(const double *rows, int stride, int W, int ncfg, double *_
 // PACKED output (SURVEY 8e's gather message: one (N, 16 + 6n) array, row = [T row-major 4x4 | J (6,n) C-order]): the wave writes `ncfg` staged
 // rows of 16 + W doubles as ONE contiguous run -- a single write stream per launch, where the two-array form has two.  T and J are staged in
 // separate LDS areas (rowsT: 17-double rows; rowsJ: `strideJ`-double rows); 16 and W are even, so a 16-byte piece never straddles the two.
-template <bool NT = true>
-RTB_HD void kin_flush_packed(const double *rowsT, const double *rowsJ, int strideJ, int W, int ncfg, double *__restrict__ dst, int lane)
+template <bool NT = true, class S>
+RTB_HD void kin_flush_packed(const double *rowsT, const double *rowsJ, int strideJ, int W, int ncfg, S *__restrict__ dst, int lane)
 {
     const int PW = 16 + W;
     const int total = ncfg * PW;
@@ -127,6 +158,13 @@ RTB_HD void kin_flush_packed(const double *rowsT, const double *rowsJ, int strid
     const int da = 128 / PW, db = 128 - da * PW;
     for (; f < total; f += 128) {
         const double *src = e < 16 ? rowsT + cfg * 17 + e : rowsJ + cfg * strideJ + (e - 16);
+        if constexpr (sizeof(S) == 4) {
+            store_pair_f32<NT>(dst + f, src[0], src[1]);
+            e += db;
+            cfg += da;
+            if (e >= PW) { e -= PW; cfg += 1; }
+            continue;
+        }
         double2 v;
         v.x = src[0];
         v.y = src[1];
@@ -169,12 +207,17 @@ __device__ __forceinline__ void flush_run(const double *rows, int stride, int W,
 #endif
 
 // un-coalesced alternative (A/B baseline): every lane stores its own row straight from LDS
-RTB_HD void kin_store_own(const double *rows, int stride, int W, bool live, double *__restrict__ dst_row,
+template <class S>
+RTB_HD void kin_store_own(const double *rows, int stride, int W, bool live, S *__restrict__ dst_row,
                           int lane)
 {
     if (!live) return;
     const double *mine = rows + lane * stride;
     for (int e = 0; e < W; e += 2) {
+        if constexpr (sizeof(S) == 4) {
+            store_pair_f32<false>(dst_row + e, mine[e], mine[e + 1]);
+            continue;
+        }
         double2 v;
         v.x = mine[e];
         v.y = mine[e + 1];

@@ -69,6 +69,66 @@ __device__ __forceinline__ void tile_copy(double *rows, int stride, int col_off,
     }
 }
 
+// ---- float32 rows (rtbhip_rne_f32): q / qd / qdd arrive and tau leaves as floats; the LDS tile and the recursions are the fp64 ones.
+// A float tile is half as long in bytes, so the 8-byte-per-lane trips of the fp64 copies would become 4-byte ones -- twice the instructions per
+// byte, each wave-instruction down to two lines.  Here a lane moves a PIECE of four consecutive floats (16 bytes, the widest access; a wave
+// trip = 1 KiB contiguous): the Panda's 64 x 7 tile is 112 pieces per array, two trips, six loads in flight for the three arrays (fp64: 21
+// of 8 bytes).  A piece straddles rows (n is not a multiple of 4 in general): each of its floats is widened and placed on its own.  The last
+// piece of a ragged tail is moved float by float -- nothing is read or written past `count`.  Pointers are only assumed 4-byte aligned.
+constexpr int kF32Piece = 4;
+typedef float rne_v4f __attribute__((ext_vector_type(4)));
+typedef rne_v4f rne_v4f_a4 __attribute__((aligned(4)));
+__device__ __forceinline__ rne_v4f piece_load(const float *__restrict__ g, int f, int count)
+{
+    rne_v4f v = {0.f, 0.f, 0.f, 0.f};
+    if (!g) return v;                                               // NULL qd / qdd = zeros
+    if (f + kF32Piece <= count) return *reinterpret_cast<const rne_v4f_a4 *>(g + f);
+#pragma unroll
+    for (int i = 0; i < kF32Piece; ++i)
+        if (f + i < count) v[i] = g[f + i];
+    return v;
+}
+__device__ __forceinline__ void piece_store(float *__restrict__ g, int f, int count, rne_v4f v)
+{
+    if (f + kF32Piece <= count) { __builtin_nontemporal_store(v, reinterpret_cast<rne_v4f_a4 *>(g + f)); return; }
+#pragma unroll
+    for (int i = 0; i < kF32Piece; ++i)
+        if (f + i < count) __builtin_nontemporal_store(v[i], g + f + i);
+}
+
+// tile_copy for float rows and a run-time n: pieces lane, lane + 64, ... of the run, two loads in flight per trip on the way in
+template <bool TO_LDS>
+__device__ __forceinline__ void tile_copy_f32(double *rows, int stride, int col_off, int n, int count,
+                                              const float *__restrict__ gsrc, float *__restrict__ gdst, int lane)
+{
+    constexpr int kStep = kF32Piece * kW;
+    auto place = [&](int f, rne_v4f &v) {                           // floats f .. f + 3 of the run <-> rows[row][col_off + col]
+        int r = f / n, c = f - r * n;
+#pragma unroll
+        for (int i = 0; i < kF32Piece; ++i) {
+            if (f + i < count) {
+                if (TO_LDS) rows[r * stride + col_off + c] = (double)v[i];
+                else v[i] = (float)rows[r * stride + col_off + c];
+            }
+            if (++c == n) { c = 0; r += 1; }
+        }
+    };
+    int f = kF32Piece * lane;
+    if (TO_LDS) {
+        for (; f + kStep < count; f += 2 * kStep) {
+            rne_v4f v0 = piece_load(gsrc, f, count), v1 = piece_load(gsrc, f + kStep, count);
+            place(f, v0);
+            place(f + kStep, v1);
+        }
+    }
+    for (; f < count; f += kStep) {
+        rne_v4f v = {0.f, 0.f, 0.f, 0.f};
+        if (TO_LDS) v = piece_load(gsrc, f, count);
+        place(f, v);
+        if (!TO_LDS) piece_store(gdst, f, count, v);
+    }
+}
+
 #ifndef RTB_RNE_WAVES
 #define RTB_RNE_WAVES 2   // waves per SIMD the register allocator must leave room for (<= 256 VGPRs)
 #endif
@@ -77,11 +137,13 @@ __device__ __forceinline__ void tile_copy(double *rows, int stride, int col_off,
 // recursion with the LDS row as the accessor target (q is read once, up front; qd/qdd are re-read
 // from LDS where they are used, so they occupy no registers across the recursions; tau overwrites the
 // q slots, which are dead by then), write the torques back coalesced.
-template <int NJ, bool MDH, bool ALLREV, bool ATREST = false, RneSig SIG = 0>
+// S: the storage type of q, qd, qdd and tau -- double, or float (the _f32 kernels below: widened after the load, rounded once before the store)
+template <int NJ, bool MDH, bool ALLREV, bool ATREST = false, RneSig SIG = 0, class S>
 __device__ __forceinline__ void rne_tile(const RneParams &rp, ConstLinks links, int n, int stride, int64_t tile,
-                                         const double *__restrict__ q, const double *__restrict__ qd,
-                                         const double *__restrict__ qdd, double *__restrict__ tau, double *lds, int lane)
+                                         const S *__restrict__ q, const S *__restrict__ qd,
+                                         const S *__restrict__ qdd, S *__restrict__ tau, double *lds, int lane)
 {
+    constexpr bool kF32 = sizeof(S) == 4;
     const V3 grav = v3(rp.grav[0], rp.grav[1], rp.grav[2]);
     const V3 ftip = rp.has_fext ? v3(rp.fext[0], rp.fext[1], rp.fext[2]) : v3(0, 0, 0);
     const V3 ntip = rp.has_fext ? v3(rp.fext[3], rp.fext[4], rp.fext[5]) : v3(0, 0, 0);
@@ -90,7 +152,37 @@ __device__ __forceinline__ void rne_tile(const RneParams &rp, ConstLinks links, 
     const int64_t left = rp.N - cfg0;
     const int ncfg = left < kW ? (int)left : kW;
     const int count = ncfg * n;
-    if (NJ > 0) {
+    if constexpr (NJ > 0 && kF32) {
+        // all 3 * ceil(NJ / 4) coalesced 16-byte loads of the tile in flight at once, then the widening LDS transposition
+        constexpr int C = NJ > 0 ? NJ : 1, P = (kW * C + kF32Piece * kW - 1) / (kF32Piece * kW);
+        rne_v4f r0[P], r1[P], r2[P];
+        const float *g0 = (const float *)q + cfg0 * NJ, *g1 = qd ? (const float *)qd + cfg0 * NJ : nullptr, *g2 = qdd ? (const float *)qdd + cfg0 * NJ : nullptr;
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            const int f = kF32Piece * (lane + kW * k);
+            r0[k] = piece_load(g0, f, count);
+            r1[k] = piece_load(g1, f, count);
+            r2[k] = piece_load(g2, f, count);
+        }
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+#pragma unroll
+            for (int i = 0; i < kF32Piece; ++i) {
+                const int f = kF32Piece * (lane + kW * k) + i;
+                if (f < kW * C) {                                  // (the last trip's pieces may lie past the tile)
+                    const int r = f / C, c = f - r * C;
+                    double *dst = lds + r * stride + c;
+                    dst[0] = (double)r0[k][i];
+                    dst[C] = (double)r1[k][i];
+                    dst[2 * C] = (double)r2[k][i];
+                }
+            }
+        }
+    } else if constexpr (NJ == 0 && kF32) {
+        tile_copy_f32<true>(lds, stride, 0, n, count, (const float *)q + cfg0 * n, nullptr, lane);
+        tile_copy_f32<true>(lds, stride, n, n, count, qd ? (const float *)qd + cfg0 * n : nullptr, nullptr, lane);
+        tile_copy_f32<true>(lds, stride, 2 * n, n, count, qdd ? (const float *)qdd + cfg0 * n : nullptr, nullptr, lane);
+    } else if constexpr (NJ > 0) {
         // all 3*NJ coalesced 8-byte loads of the tile in flight at once (a run-time-trip-count copy
         // loop serialises load -> wait -> LDS write: 21 dependent HBM round trips per tile measured as
         // 65 % of the wave lifetime in s_waitcnt), then the LDS transposition.
@@ -138,7 +230,24 @@ __device__ __forceinline__ void rne_tile(const RneParams &rp, ConstLinks links, 
                               [&](int j) { return mine[2 * n + j]; }, [&](int j, double v) { mine[j] = v; });
     }
     __syncthreads();
-    if (NJ > 0) {
+    if constexpr (NJ > 0 && kF32) {
+        constexpr int C = NJ > 0 ? NJ : 1, P = (kW * C + kF32Piece * kW - 1) / (kF32Piece * kW);
+        float *g = (float *)tau + cfg0 * NJ;
+        rne_v4f r0[P];
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+#pragma unroll
+            for (int i = 0; i < kF32Piece; ++i) {
+                const int f = kF32Piece * (lane + kW * k) + i;
+                const int r = f / C, c = f - r * C;
+                r0[k][i] = f < kW * C ? (float)lds[r * stride + c] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < P; ++k) piece_store(g, kF32Piece * (lane + kW * k), count, r0[k]);
+    } else if constexpr (NJ == 0 && kF32) {
+        tile_copy_f32<false>(lds, stride, 0, n, count, nullptr, (float *)tau + cfg0 * n, lane);
+    } else if constexpr (NJ > 0) {
         constexpr int C = NJ > 0 ? NJ : 1;
         double *g = tau + cfg0 * NJ;
         double r0[C];
@@ -166,6 +275,17 @@ template <int NJ, bool MDH, bool ALLREV, RneSig SIG = 0>
 __global__ __launch_bounds__(kW, (SIG ? 3 : RTB_RNE_WAVES)) void k_rne(RneParams rp, const DevLink *links_g, const double *__restrict__ q,
                                            const double *__restrict__ qd, const double *__restrict__ qdd,
                                            double *__restrict__ tau)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    rne_tile<NJ, MDH, ALLREV, false, SIG>(rp, (ConstLinks)links_g, NJ, rne_stride(NJ), blockIdx.x, q, qd, qdd, tau, lds, threadIdx.x);
+}
+
+// float32 q / qd / qdd / tau (rtbhip_rne_f32): the same tile, the same launch shape and LDS request (the tile is fp64); SIG != 0 only for the
+// signatures built into the library (Panda, Puma560)
+template <int NJ, bool MDH, bool ALLREV, RneSig SIG = 0>
+__global__ __launch_bounds__(kW, (SIG ? 3 : RTB_RNE_WAVES)) void k_rne_f32(RneParams rp, const DevLink *links_g, const float *__restrict__ q,
+                                               const float *__restrict__ qd, const float *__restrict__ qdd,
+                                               float *__restrict__ tau)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     rne_tile<NJ, MDH, ALLREV, false, SIG>(rp, (ConstLinks)links_g, NJ, rne_stride(NJ), blockIdx.x, q, qd, qdd, tau, lds, threadIdx.x);
@@ -212,7 +332,7 @@ __global__ __launch_bounds__(kW, RTB_RNE_WAVES) void k_rne_atrest(RneParams rp, 
                                                   const double *__restrict__ qdd, double *__restrict__ tau)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    rne_tile<NJ, MDH, true, true, SIG>(rp, (ConstLinks)links_g, NJ, rne_stride(NJ), blockIdx.x, q, nullptr, qdd, tau, lds, threadIdx.x);
+    rne_tile<NJ, MDH, true, true, SIG>(rp, (ConstLinks)links_g, NJ, rne_stride(NJ), blockIdx.x, q, (const double *)nullptr, qdd, tau, lds, threadIdx.x);
 }
 
 // run-time joint count (n > 8): grid-stride over tiles, per-link state in private memory
@@ -220,6 +340,21 @@ template <bool MDH>
 __global__ __launch_bounds__(kW) void k_rne_rt(RneParams rp, const DevLink *links_g, const double *__restrict__ q,
                                               const double *__restrict__ qd, const double *__restrict__ qdd,
                                               double *__restrict__ tau)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int n = rp.n;
+    const int stride = rne_stride(n);
+    const int64_t tiles = (rp.N + kW - 1) / kW;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        rne_tile<0, MDH, false>(rp, (ConstLinks)links_g, n, stride, tile, q, qd, qdd, tau, lds, threadIdx.x);
+        __syncthreads();
+    }
+}
+
+template <bool MDH>
+__global__ __launch_bounds__(kW) void k_rne_rt_f32(RneParams rp, const DevLink *links_g, const float *__restrict__ q,
+                                                  const float *__restrict__ qd, const float *__restrict__ qdd,
+                                                  float *__restrict__ tau)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int n = rp.n;
@@ -324,6 +459,68 @@ static void launch_rt(bool mdh, dim3 grid, size_t lds, hipStream_t s, const RneP
 {
     if (mdh) hipLaunchKernelGGL((k_rne_rt<true>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
     else hipLaunchKernelGGL((k_rne_rt<false>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
+}
+
+// float32 rows: the built-in structure instantiations (Panda, Puma560) and the general kernels, by the rules of launch_nj -- minus the run-time
+// instantiations (hipRTC compiles fp64 kernels only: a robot that would take one is served by its general kernel, the same numbers), the
+// at-rest kernels (a NULL qd reads as zeros in the general kernel) and the A/B launch shapes
+template <int NJ>
+static void launch_nj_f32(bool mdh, bool allrev, dim3 grid, size_t lds, hipStream_t s, const RneParams &rp, const DevLink *links,
+                          const float *q, const float *qd, const float *qdd, float *tau, RneSig sig)
+{
+    if constexpr (NJ == 7) {
+        if (sig == kRneSigPanda && mdh && qd && jit_builtin_enabled()) { hipLaunchKernelGGL((k_rne_f32<7, true, true, kRneSigPanda>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau); return; }
+    }
+    if constexpr (NJ == 6) {
+        if (sig == kRneSigPuma560 && !mdh && qd && jit_builtin_enabled()) { hipLaunchKernelGGL((k_rne_f32<6, false, true, kRneSigPuma560>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau); return; }
+    }
+    if (mdh && allrev) hipLaunchKernelGGL((k_rne_f32<NJ, true, true>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
+    else if (mdh) hipLaunchKernelGGL((k_rne_f32<NJ, true, false>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
+    else if (allrev) hipLaunchKernelGGL((k_rne_f32<NJ, false, true>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
+    else hipLaunchKernelGGL((k_rne_f32<NJ, false, false>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
+}
+
+int launch_rne_f32(const Dyn *d, const DevLink *links, const float *q, const float *qd, const float *qdd,
+                   int64_t N, const double *grav3, const double *fext6, float *tau, hipStream_t s)
+{
+    if (N == 0) return RTBHIP_OK;
+    RneParams rp;
+    rp.n = d->n;
+    rp.has_fext = fext6 != nullptr;
+    rp.N = N;
+    rp.wbase = nullptr;
+    for (int i = 0; i < 3; i++) rp.grav[i] = grav3[i];
+    for (int i = 0; i < 6; i++) rp.fext[i] = fext6 ? fext6[i] : 0.0;
+    int stride = 3 * d->n;
+    if (!(stride & 1)) stride += 1;
+    const size_t lds = (size_t)kW * stride * sizeof(double);
+    const int64_t tiles = (N + kW - 1) / kW;
+    const bool mdh = d->mdh != 0;
+    bool allrev = true;
+    for (const DevLink &l : d->links) allrev = allrev && l.sigma == 0;
+    const bool rt = d->n > 8 || tiles > 0x7fffffff;
+    int64_t g = rt ? (tiles + g_rne_tiles_per_wave - 1) / g_rne_tiles_per_wave : tiles;
+    if (g > 0x7fffffff) g = 0x7fffffff;
+    dim3 grid((unsigned)g);
+    const RneSig sig = (g_rne_sig && !rt && !g_rne_persist && g_rne_wpb == 1) ? rne_signature(d->links.data(), d->n) : 0;
+    switch (rt ? 0 : d->n) {
+    case 1: launch_nj_f32<1>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
+    case 2: launch_nj_f32<2>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
+    case 3: launch_nj_f32<3>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
+    case 4: launch_nj_f32<4>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
+    case 5: launch_nj_f32<5>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
+    case 6: launch_nj_f32<6>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
+    case 7: launch_nj_f32<7>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
+    case 8: launch_nj_f32<8>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
+    default:
+        if (mdh) hipLaunchKernelGGL((k_rne_rt_f32<true>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
+        else hipLaunchKernelGGL((k_rne_rt_f32<false>), grid, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
+        break;
+    }
+    note_launch((int)grid.x, kW, (int)lds);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "k_rne_f32 launch");
+    return RTBHIP_OK;
 }
 
 int launch_rne(const Dyn *d, const DevLink *links, const double *q, const double *qd, const double *qdd,

@@ -254,6 +254,11 @@ int launch_kin(const Chain *c, const DevChain &dc, const double *q, int64_t N, c
 
 int launch_kin_packed(const Chain *c, const DevChain &dc, const double *q, int64_t N, const Affine &base,
                       const Affine &tool, int frame, double *TJ, hipStream_t s);
+// float32 rows in, float32 rows out (fp64 arithmetic): T or J may be NULL
+int launch_kin_f32(const Chain *c, const DevChain &dc, const float *q, int64_t N, const Affine &base,
+                   const Affine &tool, int frame, float *T, float *J, hipStream_t s);
+int launch_kin_packed_f32(const Chain *c, const DevChain &dc, const float *q, int64_t N, const Affine &base,
+                          const Affine &tool, int frame, float *TJ, hipStream_t s);
 
 int launch_kin_diff(const Chain *c, const DevChain &dc, int mode, int axes, const double *q, const double *qd, int64_t N,
                     const Affine &tool, int frame, double *out, hipStream_t s);
@@ -285,6 +290,9 @@ int launch_fleet(const std::vector<FleetEntry> &entries, int frame, hipStream_t 
 int launch_rne(const Dyn *d, const DevLink *links, const double *q, const double *qd,
                const double *qdd, int64_t N, const double *grav3, const double *fext6, double *tau,
                hipStream_t s, double *wbase = nullptr);   // wbase (N,6): base wrench as well (run-time-n kernel)
+int launch_rne_f32(const Dyn *d, const DevLink *links, const float *q, const float *qd,
+                   const float *qdd, int64_t N, const double *grav3, const double *fext6, float *tau,
+                   hipStream_t s);                        // float32 rows (fp64 arithmetic); no base wrench
 
 int launch_dyn(const Dyn *d, const DevLink *links, int mode, const double *q, const double *qd, const double *tq,
                int64_t N, const double *grav3, double *out, hipStream_t s);

@@ -65,6 +65,8 @@ SIGNATURES = {
     "rtbhip_jacob": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_fkine_jacob": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "rtbhip_fkine_jacob_packed": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "rtbhip_fkine_jacob_f32": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "rtbhip_fkine_jacob_packed_f32": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_hessian": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_hessian_from_jacobian": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp]),
     "rtbhip_manipulability_from_jacobian": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
@@ -83,6 +85,7 @@ SIGNATURES = {
     "rtbhip_dyn_create": (C.c_int, [_vp, _i32, _i32, C.POINTER(_u64)]),
     "rtbhip_dyn_destroy": (C.c_int, [_u64]),
     "rtbhip_rne": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "rtbhip_rne_f32": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
     "rtbhip_rne_base_wrench": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
     "rtbhip_jacob_dot": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_jacob0_dot_analytical": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),
@@ -219,6 +222,23 @@ def shard_range(N, rank, world):
 # ---------------------------------------------------------------- buffer plumbing
 def is_torch(x):
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
+
+
+def device_dtype(tensors, f32_ok=False, what="device inputs"):
+    """The one element type of the CUDA tensors of a call (None entries skipped) -- their pointers are handed to a kernel that reads that type, so
+    anything else is refused here, never reinterpreted: float64, and float32 where the call has a float32 entry point (f32_ok: ETS fkine / eval /
+    jacob0 / jacobe / fkine_jacob0 and DHRobot.rne).  TypeError for a mix of element types and for any other type.  -> True for float32."""
+    import torch
+    kinds = []
+    for x in tensors:
+        if x is not None and is_torch(x) and x.dtype not in kinds:
+            kinds.append(x.dtype)
+    if len(kinds) > 1:
+        raise TypeError("%s must share one dtype, got %s" % (what, ", ".join(str(k) for k in kinds)))
+    ok = (torch.float64, torch.float32) if f32_ok else (torch.float64,)
+    if kinds and kinds[0] not in ok:
+        raise TypeError("%s must be %s, got %s" % (what, " or ".join(str(k) for k in ok), kinds[0]))
+    return bool(kinds) and kinds[0] == torch.float32
 
 
 def host_ptr(a):

@@ -484,13 +484,15 @@ class DHRobot(RobotKinematics):
         check(lib().rtbhip_dyn_upload(self._dyn_handle(), dev))
         return self
 
-    def _dyn_args(self, arrays):
-        """-> (list of (N,n) contiguous arrays or None, N, single, torch_mode, ptr(), stream, mem, device)"""
+    def _dyn_args(self, arrays, f32_ok=False):
+        """-> (list of (N,n) contiguous arrays or None, N, single, torch_mode, ptr(), stream, mem, device)
+        Device tensors must all be float64 -- or all float32 where the caller has a float32 entry point (f32_ok: rne) -- TypeError otherwise."""
         n = self.n
         first = next(x for x in arrays if x is not None)
         tm = is_torch(first) and first.is_cuda
         out = []
         if tm:
+            _lib.device_dtype(arrays, f32_ok)
             single = first.dim() == 1
             for x in arrays:
                 out.append(None if x is None else x.reshape(-1, n).contiguous())
@@ -524,7 +526,10 @@ class DHRobot(RobotKinematics):
     def rne(self, q, qd=None, qdd=None, gravity=None, fext=None, base_wrench=False):
         """Inverse dynamics tau(q, qd, qdd): (n,) or (N,n)
         (reference robot/DHRobot.py:1373-1456 -> frne.frne core/frne.c:106-230).
-        qd / qdd = None means zeros (no zero arrays are read by the kernel)."""
+        qd / qdd = None means zeros (no zero arrays are read by the kernel).
+        float32 CUDA tensors (all of q, qd, qdd; a mix is a TypeError) give a float32 tau: rtbhip_rne_f32 -- fp64 arithmetic, each torque rounded once,
+        equal to `rne(q.double(), ...).float()` bit for bit at half the bytes.  Served by the kernels built into the library (the general ones,
+        the Panda and Puma560 instantiations), not by run-time instantiations; not with base_wrench=True.  NumPy float32 is converted on the host."""
         if base_wrench:
             # robot/DHRobot.py:1409-1412 sends base_wrench=True to rne_python (:1458-1796), which returns (tau, wbase) with
             # wbase = [R_1 f_1, R_1 n_1] (:1765-1770): the wrench the base exerts on link 1 as the backward recursion holds it when it ends,
@@ -545,9 +550,15 @@ class DHRobot(RobotKinematics):
             check(lib().rtbhip_rne_base_wrench(self._dyn_handle(), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), N, host_ptr(gc),
                                                host_ptr(f), ptr(tau), ptr(wb), mem, stream))
             return (tau[0], wb[0]) if single else (tau, wb)
-        arrs, N, single, tm, ptr, stream, mem, dev = self._dyn_args([q, qd, qdd])
+        arrs, N, single, tm, ptr, stream, mem, dev = self._dyn_args([q, qd, qdd], f32_ok=True)
         gc = self._gravity_c(gravity)
         f = None if fext is None else np.ascontiguousarray(np.asarray(fext, dtype=np.float64).reshape(6))
+        if tm and _lib.device_dtype(arrs, True):
+            import torch
+            tau = torch.empty((N, self.n), dtype=torch.float32, device=dev)
+            check(lib().rtbhip_rne_f32(self._dyn_handle(), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), N, host_ptr(gc),
+                                       host_ptr(f), ptr(tau), mem, stream))
+            return tau[0] if single else tau
         tau = self._empty((N, self.n), tm, dev)
         check(lib().rtbhip_rne(self._dyn_handle(), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), N, host_ptr(gc),
                                host_ptr(f), ptr(tau), mem, stream))
@@ -556,10 +567,12 @@ class DHRobot(RobotKinematics):
     # ---- the Dynamics-mixin terms (reference robot/Dynamics.py), one fused kernel each
     def gravload(self, q=None, gravity=None):
         """tau_g(q) (reference Dynamics.gravload robot/Dynamics.py:863-922): rne(q, 0, 0)."""
+        _lib.device_dtype([q])                       # (float32 is served by rne itself only)
         return self.rne(q, None, None, gravity=gravity)
 
     def itorque(self, q, qdd):
         """M(q) qdd (reference Dynamics.itorque robot/Dynamics.py:1407-1465): rne(q, 0, qdd) without gravity."""
+        _lib.device_dtype([q, qdd])
         return self.rne(q, None, qdd, gravity=[0, 0, 0])
 
     def inertia(self, q):

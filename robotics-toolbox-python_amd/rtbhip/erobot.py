@@ -469,6 +469,7 @@ class ERobot(RobotKinematics):
         first = q
         tm = is_torch(first) and first.is_cuda
         if tm:
+            _lib.device_dtype((q, qd, qdd))            # the kernel reads doubles: any other element type is refused, not reinterpreted
             single = q.dim() == 1
             arrs = [None if x is None else x.reshape(-1, n).contiguous() for x in (q, qd, qdd)]
         else:
@@ -497,6 +498,7 @@ class ERobot(RobotKinematics):
         n = self.n
         tm = is_torch(arrays[0]) and arrays[0].is_cuda
         if tm:
+            _lib.device_dtype(arrays)
             single = arrays[0].dim() == 1
             arrs = [x.reshape(-1, n).contiguous() for x in arrays]
         else:

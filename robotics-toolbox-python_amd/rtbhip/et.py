@@ -677,15 +677,19 @@ class ETS:
         self._drop_handle()
 
     # ------------------------------------------------------------ argument shaping
-    def _shape_q(self, q):
+    def _shape_q(self, q, f32_ok=False):
         """-> (q2d, single, torch_mode).  1-D, (1,n) and (n,1) are ONE configuration
-        (reference core/fknm.cpp:964-988); anything else is a trajectory of rows."""
+        (reference core/fknm.cpp:964-988); anything else is a trajectory of rows.
+        f32_ok: the caller has a float32 entry point (eval / fkine, jacob0, jacobe, fkine_jacob0) -- a float32 device q then stays float32 and the
+        caller returns float32 tensors; every other method refuses it.  A host array of any numeric type becomes float64 as before."""
         qw = self.q_width
         if is_torch(q):
             import torch
             if not q.is_cuda:
                 return self._shape_q(q.detach().numpy())
-            if q.dtype != torch.float64:
+            if f32_ok:
+                _lib.device_dtype([q], True, "device q")
+            elif q.dtype != torch.float64:
                 raise TypeError("device q must be float64")
             single = q.dim() == 1 or (q.dim() == 2 and self._one_config(tuple(q.shape), qw))
             q2 = q.reshape(1, -1) if single else q
@@ -727,6 +731,11 @@ class ETS:
         return _lib.host_empty(shape, dtype or np.float64)      # pinned from 1 MB up: the D2H DMA writes into it directly
 
     @staticmethod
+    def _f32(q2, torch_mode):
+        """a float32 device q (after _shape_q(f32_ok=True)): the call takes the library's _f32 entry point"""
+        return torch_mode and q2.element_size() == 4
+
+    @staticmethod
     def _ptr(x, torch_mode):
         if x is None:
             return None
@@ -739,12 +748,19 @@ class ETS:
     # ------------------------------------------------------------ kinematics
     def eval(self, q, base=None, tool=None, include_base=True):
         """Forward kinematics as ndarray: (4,4) for one q, (N,4,4) for a trajectory
-        (reference ETS.eval robot/ETS.py:1021-1141 -> ETS_fkine core/fknm.cpp:923-1064)."""
-        q2, single, tm = self._shape_q(q)
+        (reference ETS.eval robot/ETS.py:1021-1141 -> ETS_fkine core/fknm.cpp:923-1064).
+        A float32 CUDA q gives a float32 tensor (rtbhip_fkine_jacob_f32: fp64 arithmetic, each entry rounded once -- equal to
+        `eval(q.double()).float()` bit for bit, half the bytes); so do jacob0, jacobe and fkine_jacob0.  NumPy float32 is converted on the host."""
+        q2, single, tm = self._shape_q(q, f32_ok=True)
         N = q2.shape[0]
-        T = self._out((N, 4, 4), q2, tm)
         b = small(base, 16) if (base is not None and include_base) else None
         t = small(tool, 16)
+        if self._f32(q2, tm):
+            T = self._out((N, 4, 4), q2, tm, q2.dtype)
+            check(lib().rtbhip_fkine_jacob_f32(self._handle(), self._ptr(q2, tm), N, host_ptr(b), host_ptr(t), 0,
+                                               self._ptr(T, tm), None, MEM_DEVICE, self._stream(tm)))
+            return T[0] if single else T
+        T = self._out((N, 4, 4), q2, tm)
         check(lib().rtbhip_fkine(self._handle(), self._ptr(q2, tm), N, host_ptr(b), host_ptr(t),
                                  self._ptr(T, tm), MEM_DEVICE if tm else MEM_HOST, self._stream(tm)))
         return T[0] if single else T
@@ -767,10 +783,15 @@ class ETS:
         return _poses(self.eval(q, base=base, tool=tool, include_base=include_base))
 
     def _jac(self, q, tool, frame):
-        q2, single, tm = self._shape_q(q)
+        q2, single, tm = self._shape_q(q, f32_ok=True)
         N = q2.shape[0]
-        J = self._out((N, 6, self.n), q2, tm)
         t = small(tool, 16)
+        if self._f32(q2, tm):
+            J = self._out((N, 6, self.n), q2, tm, q2.dtype)
+            check(lib().rtbhip_fkine_jacob_f32(self._handle(), self._ptr(q2, tm), N, None, host_ptr(t), frame,
+                                               None, self._ptr(J, tm), MEM_DEVICE, self._stream(tm)))
+            return J[0] if single else J
+        J = self._out((N, 6, self.n), q2, tm)
         check(lib().rtbhip_jacob(self._handle(), self._ptr(q2, tm), N, host_ptr(t), frame,
                                  self._ptr(J, tm), MEM_DEVICE if tm else MEM_HOST, self._stream(tm)))
         return J[0] if single else J
@@ -790,32 +811,43 @@ class ETS:
         packed=True: ONE (N, 16 + 6n) array whose row i is [T[i] (16, row-major 4x4) | J[i] ((6,n) C-order)] -- the device writes a single
         stream and the row is the T||J message of the multi-GPU gather (rtbhip_fkine_jacob_packed); the returned (T, J) are strided views
         of it and `.packed` / the third item gives the array itself: `T, J, TJ = ets.fkine_jacob0(q, packed=True)`.  `out` = a TJ array of an
-        earlier call to write into."""
-        q2, single, tm = self._shape_q(q)
+        earlier call to write into; it must have q's element type (a float32 device q: float32 everywhere, see eval)."""
+        q2, single, tm = self._shape_q(q, f32_ok=True)
         N = q2.shape[0]
+        f32 = self._f32(q2, tm)
         if packed:
             w = 16 + 6 * self.n
-            TJ = self._out((N, w), q2, tm) if out is None else out
+            TJ = self._out((N, w), q2, tm, q2.dtype if f32 else None) if out is None else out
             if out is not None:
-                # the kernel (or the D2H copy) writes N * w * 8 bytes through this pointer: shape, width, contiguity, element type AND where
-                # it lives must be what q's are -- a float32 or wrong-device `out` would be overrun / written through a foreign pointer
-                import torch as _torch
-                good = (is_torch(TJ) and TJ.dtype == _torch.float64 and TJ.device == q2.device and TJ.is_contiguous()) if tm else \
-                       (isinstance(TJ, np.ndarray) and TJ.dtype == np.float64 and TJ.flags.c_contiguous and TJ.flags.writeable)
+                # the kernel (or the D2H copy) writes N * w * 8 bytes (4 for float32 rows) through this pointer: shape, width, contiguity,
+                # element type AND where it lives must be what q's are -- an `out` of another type or device would be overrun / written
+                # through a foreign pointer
+                if tm:
+                    good = is_torch(TJ) and TJ.dtype == q2.dtype and TJ.device == q2.device and TJ.is_contiguous()
+                else:
+                    good = isinstance(TJ, np.ndarray) and TJ.dtype == np.float64 and TJ.flags.c_contiguous and TJ.flags.writeable
                 if not good or tuple(TJ.shape) != (N, w):
-                    raise ValueError("out must be a contiguous (N, 16 + 6n) float64 %s" % ("tensor on q's device" if tm else "ndarray"))
+                    raise ValueError("out must be a contiguous (N, 16 + 6n) %s %s" % ("float32" if f32 else "float64", "tensor on q's device" if tm else "ndarray"))
             b, t = small(base, 16), small(tool, 16)
-            check(lib().rtbhip_fkine_jacob_packed(self._handle(), self._ptr(q2, tm), N, host_ptr(b), host_ptr(t), frame,
-                                                  self._ptr(TJ, tm), MEM_DEVICE if tm else MEM_HOST, self._stream(tm)))
+            if f32:
+                check(lib().rtbhip_fkine_jacob_packed_f32(self._handle(), self._ptr(q2, tm), N, host_ptr(b), host_ptr(t), frame,
+                                                          self._ptr(TJ, tm), MEM_DEVICE, self._stream(tm)))
+            else:
+                check(lib().rtbhip_fkine_jacob_packed(self._handle(), self._ptr(q2, tm), N, host_ptr(b), host_ptr(t), frame,
+                                                      self._ptr(TJ, tm), MEM_DEVICE if tm else MEM_HOST, self._stream(tm)))
             if tm:
                 T, J = TJ[:, :16].unflatten(1, (4, 4)), TJ[:, 16:].unflatten(1, (6, self.n))       # strided views, no copy
             else:
                 T = np.lib.stride_tricks.as_strided(TJ, (N, 4, 4), (8 * w, 32, 8))
                 J = np.lib.stride_tricks.as_strided(TJ[:, 16:], (N, 6, self.n), (8 * w, 8 * self.n, 8))
             return (T[0], J[0], TJ[0]) if single else (T, J, TJ)
-        T = self._out((N, 4, 4), q2, tm)
-        J = self._out((N, 6, self.n), q2, tm)
+        T = self._out((N, 4, 4), q2, tm, q2.dtype if f32 else None)
+        J = self._out((N, 6, self.n), q2, tm, q2.dtype if f32 else None)
         b, t = small(base, 16), small(tool, 16)
+        if f32:
+            check(lib().rtbhip_fkine_jacob_f32(self._handle(), self._ptr(q2, tm), N, host_ptr(b), host_ptr(t), frame,
+                                               self._ptr(T, tm), self._ptr(J if self.n else None, tm), MEM_DEVICE, self._stream(tm)))
+            return (T[0], J[0]) if single else (T, J)
         check(lib().rtbhip_fkine_jacob(self._handle(), self._ptr(q2, tm), N, host_ptr(b), host_ptr(t), frame,
                                        self._ptr(T, tm), self._ptr(J, tm), MEM_DEVICE if tm else MEM_HOST,
                                        self._stream(tm)))
