@@ -1,6 +1,8 @@
 // api.cpp -- the extern "C" entry points of librtbhip.so (declared in include/rtbhip.h).
 // Argument checking, handle registry, lazy per-device upload of the chain / link tables, and the
 // host-memory convenience path (stage -> launch -> copy back).  No arithmetic lives here.
+// Layout: the shared plumbing (errors, tracing, registry, uploads, staging, argument checks), then one body per entry FAMILY in an
+// anonymous namespace, then the exported functions, which only name their family and pass their arguments on.
 #include "rtbhip_internal.h"
 #include "partial_device.h"
 #include "frames_device.h"
@@ -11,10 +13,24 @@
 #include <dlfcn.h>
 #include <map>
 #include <memory>
+#include <type_traits>
 #include <unordered_map>
 #include <functional>
 
 namespace rtbhip {
+
+// defined next to the kernels they serve; not in a header: every header of csrc/ is part of the run-time compiler's source digest
+void kin_tune(const char *key, int value);
+void rne_tune(const char *key, int value);
+void ik_tune(const char *key, int value);
+void partial_tune(const char *key, int value);
+void hostpipe_tune(const char *key, int value);
+void shard_tune(const char *key, int value);
+void tree_tune(const char *key, int value);
+void ik_release_device_state();
+int ik_prepare_device();
+std::string tree_jit_knowledge(const Tree *t, std::string *type_name);      // tree_kernels.hip
+bool tree_jit_applies(const Tree *t);
 
 // ---------------------------------------------------------------- errors
 static thread_local std::string g_err;
@@ -55,51 +71,116 @@ struct Roctx {
     }
 };
 const Roctx &roctx() { static const Roctx r; return r; }
-struct TraceRange {
+struct TraceRange {       // named "rtbhip_" + fn; the name is only built when tracing is on
     bool on;
-    explicit TraceRange(const char *name) : on(roctx().push != nullptr) { if (on) roctx().push(name); }
+    explicit TraceRange(const char *fn) : on(roctx().push != nullptr) { if (on) roctx().push((std::string("rtbhip_") + fn).c_str()); }
     ~TraceRange() { if (on) roctx().pop(); }
     TraceRange(const TraceRange &) = delete;
 };
 }  // namespace
-#define RTB_TRACE(name) ::rtbhip::TraceRange _trace_range(name)
+#define RTB_TRACE(fn) ::rtbhip::TraceRange _trace_range(fn)
+#define RTB_TRY(expr)                   \
+    do {                                \
+        int _rc = (expr);               \
+        if (_rc != RTBHIP_OK) return _rc; \
+    } while (0)
 
 // ---------------------------------------------------------------- handle registry
 // The registries are heap objects that are never destroyed: handles that are still registered when the process exits (module-level
 // robot objects whose Python __del__ never ran) must not have their destructors -- which call hipFree -- run during static
 // destruction, possibly after the HIP runtime has been torn down.  The OS reclaims device memory with the process.
-static std::mutex &g_reg_mu = *new std::mutex();
-static std::unordered_map<uint64_t, std::shared_ptr<Chain>> &g_chains = *new std::unordered_map<uint64_t, std::shared_ptr<Chain>>();
-static std::unordered_map<uint64_t, std::shared_ptr<Dyn>> &g_dyns = *new std::unordered_map<uint64_t, std::shared_ptr<Dyn>>();
-static std::unordered_map<uint64_t, std::shared_ptr<Tree>> &g_trees = *new std::unordered_map<uint64_t, std::shared_ptr<Tree>>();
+// One id counter serves all kinds, so a chain id is never a valid dyn or tree id.
 static std::atomic<uint64_t> g_next{1};
+namespace {
+template <class T> struct Registry {
+    std::mutex mu;
+    std::unordered_map<uint64_t, std::shared_ptr<T>> map;
+    uint64_t add(std::shared_ptr<T> obj)
+    {
+        const uint64_t h = g_next.fetch_add(1);
+        std::lock_guard<std::mutex> lk(mu);
+        map[h] = std::move(obj);
+        return h;
+    }
+    std::shared_ptr<T> find(uint64_t h)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = map.find(h);
+        return it == map.end() ? nullptr : it->second;
+    }
+    std::shared_ptr<T> take(uint64_t h)          // the registry's reference leaves with the caller: the object goes with its last user
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = map.find(h);
+        if (it == map.end()) return nullptr;
+        std::shared_ptr<T> obj = std::move(it->second);
+        map.erase(it);
+        return obj;
+    }
+    int destroy(uint64_t h, const char *fn)
+    {
+        if (!take(h)) { set_error(std::string(fn) + ": unknown handle"); return RTBHIP_EINVAL; }
+        return RTBHIP_OK;
+    }
+};
+Registry<Chain> &g_chains = *new Registry<Chain>();
+Registry<Dyn> &g_dyns = *new Registry<Dyn>();
+Registry<Tree> &g_trees = *new Registry<Tree>();
 
-std::shared_ptr<Chain> chain_from_handle(rtbhip_chain_t h)
+// ---------------------------------------------------------------- per-device copies of a handle's tables
+template <class P> void free_all(std::map<int, P *> &copies)
 {
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    auto it = g_chains.find(h);
-    return it == g_chains.end() ? nullptr : it->second;
+    for (auto &kv : copies) (void)hipFree(kv.second);
+    copies.clear();
 }
-std::shared_ptr<Dyn> dyn_from_handle(rtbhip_dyn_t h)
+void drop_device_copies(Chain &c) { free_all(c.dev_ops); free_all(c.dev_qlim); }
+void drop_device_copies(Dyn &d) { free_all(d.dev_links); }
+void drop_device_copies(Tree &t) { free_all(t.dev_groups); }
+// rtbhip_shutdown: handles stay valid, the tables are uploaded again on next use
+template <class T> void drop_all_device_copies(Registry<T> &reg)
 {
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    auto it = g_dyns.find(h);
-    return it == g_dyns.end() ? nullptr : it->second;
+    std::lock_guard<std::mutex> lk(reg.mu);
+    for (auto &kv : reg.map) {
+        std::lock_guard<std::mutex> l2(kv.second->mu);
+        drop_device_copies(*kv.second);
+    }
 }
 
-std::shared_ptr<Tree> tree_from_handle(rtbhip_tree_t h)
+// a device block of `alloc` bytes holding the first `bytes` of `host`; nothing stays allocated on failure
+hipError_t upload_block(const void *host, size_t bytes, size_t alloc, void **out)
 {
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    auto it = g_trees.find(h);
-    return it == g_trees.end() ? nullptr : it->second;
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, alloc);
+    if (e == hipSuccess && bytes) e = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess && p) { (void)hipFree(p); p = nullptr; }
+    *out = p;
+    return e;
 }
+// an object's one table on the current device, uploaded on first use
+template <class P> int device_table(std::mutex &mu, std::map<int, P *> &copies, const std::vector<P> &table, const char *what, const P **out)
+{
+    int dev = 0;
+    RTB_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = copies.find(dev);
+    if (it == copies.end()) {
+        void *p = nullptr;
+        hipError_t e = upload_block(table.data(), table.size() * sizeof(P), table.size() * sizeof(P), &p);
+        if (e != hipSuccess) return hip_fail(e, what);
+        it = copies.emplace(dev, (P *)p).first;
+    }
+    *out = it->second;
+    return RTBHIP_OK;
+}
+}  // namespace
 
-Chain::~Chain()
-{
-    for (auto &kv : dev_ops) (void)hipFree(kv.second);
-    for (auto &kv : dev_qlim) (void)hipFree(kv.second);
-}
-Dyn::~Dyn() { for (auto &kv : dev_links) (void)hipFree(kv.second); }
+std::shared_ptr<Chain> chain_from_handle(rtbhip_chain_t h) { return g_chains.find(h); }
+std::shared_ptr<Dyn> dyn_from_handle(rtbhip_dyn_t h) { return g_dyns.find(h); }
+std::shared_ptr<Tree> tree_from_handle(rtbhip_tree_t h) { return g_trees.find(h); }
+
+Chain::~Chain() { drop_device_copies(*this); }
+Dyn::~Dyn() { drop_device_copies(*this); }
+Tree::~Tree() { drop_device_copies(*this); }
 
 static DevChain view_of(const Chain *c, const void *base)
 {
@@ -131,61 +212,23 @@ int chain_device_ops(Chain *c, DevChain *out, const double **qlim_out)
         std::memcpy(w, c->seg.data(), c->seg.size() * sizeof(DevSeg));
         w += c->seg.size() * sizeof(DevSeg);
         if (!c->jmeta.empty()) std::memcpy(w, c->jmeta.data(), c->jmeta.size() * sizeof(int32_t));
-        void *d = nullptr;
-        double *ql = nullptr;
-        hipError_t e = hipMalloc(&d, blob.size());
-        if (e == hipSuccess) e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc((void **)&ql, (c->qlim.size() ? c->qlim.size() : 1) * sizeof(double));
-        if (e == hipSuccess && !c->qlim.empty()) e = hipMemcpy(ql, c->qlim.data(), c->qlim.size() * sizeof(double), hipMemcpyHostToDevice);
+        void *d = nullptr, *ql = nullptr;
+        hipError_t e = upload_block(blob.data(), blob.size(), blob.size(), &d);
+        if (e == hipSuccess) e = upload_block(c->qlim.data(), c->qlim.size() * sizeof(double), (c->qlim.size() ? c->qlim.size() : 1) * sizeof(double), &ql);
         if (e != hipSuccess) {             // nothing half-uploaded stays behind
             if (d) (void)hipFree(d);
-            if (ql) (void)hipFree(ql);
             return hip_fail(e, "chain table upload");
         }
-        c->dev_ops[dev] = d;
-        c->dev_qlim[dev] = ql;
-        it = c->dev_ops.find(dev);
+        it = c->dev_ops.emplace(dev, d).first;
+        c->dev_qlim[dev] = (double *)ql;
     }
     *out = view_of(c, it->second);
     if (qlim_out) *qlim_out = c->dev_qlim[dev];
     return RTBHIP_OK;
 }
 
-int dyn_device_links(Dyn *d, const DevLink **out)
-{
-    int dev = 0;
-    RTB_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(d->mu);
-    auto it = d->dev_links.find(dev);
-    if (it == d->dev_links.end()) {
-        DevLink *p = nullptr;
-        hipError_t e = hipMalloc((void **)&p, d->links.size() * sizeof(DevLink));
-        if (e == hipSuccess) e = hipMemcpy(p, d->links.data(), d->links.size() * sizeof(DevLink), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { if (p) (void)hipFree(p); return hip_fail(e, "link table upload"); }
-        d->dev_links[dev] = p;
-        it = d->dev_links.find(dev);
-    }
-    *out = it->second;
-    return RTBHIP_OK;
-}
-
-int tree_device_groups(Tree *t, const DevGroup **out)
-{
-    int dev = 0;
-    RTB_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(t->mu);
-    auto it = t->dev_groups.find(dev);
-    if (it == t->dev_groups.end()) {
-        DevGroup *p = nullptr;
-        hipError_t e = hipMalloc((void **)&p, t->groups.size() * sizeof(DevGroup));
-        if (e == hipSuccess) e = hipMemcpy(p, t->groups.data(), t->groups.size() * sizeof(DevGroup), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { if (p) (void)hipFree(p); return hip_fail(e, "tree table upload"); }
-        t->dev_groups[dev] = p;
-        it = t->dev_groups.find(dev);
-    }
-    *out = it->second;
-    return RTBHIP_OK;
-}
+int dyn_device_links(Dyn *d, const DevLink **out) { return device_table(d->mu, d->dev_links, d->links, "link table upload", out); }
+int tree_device_groups(Tree *t, const DevGroup **out) { return device_table(t->mu, t->dev_groups, t->groups, "tree table upload", out); }
 
 // Stream-ordered temporaries (hipMallocAsync: the rows of the IK schedules, the lower-order tensors of partial_fkine0) come from the device's
 // default memory pool.  Its release threshold is 0 by default: everything freed goes back to the OS at the next synchronisation, so EVERY
@@ -215,51 +258,59 @@ int device_cu_count(int *cus)
     return RTBHIP_OK;
 }
 
-#define RTB_TRY_(expr)                  \
-    do {                                \
-        int _rc = (expr);               \
-        if (_rc != RTBHIP_OK) return _rc; \
-    } while (0)
+namespace {
 
-// ---------------------------------------------------------------- host staging helper
-// RAII device buffers of the RTBHIP_MEM_HOST path of the calls that are not row-pipelined (IK, the dynamics terms, the
-// differential-kinematics consumers ...): drawn from a cache of device blocks (hostpipe.cpp), not allocated per call.
+// ---------------------------------------------------------------- the staged host path
+// The calls that are not row-pipelined (IK, the dynamics terms, the differential-kinematics consumers ...) name each buffer once, through
+// in() / out(), and spell their launch once, on the pointers those return and on stream().  RTBHIP_MEM_DEVICE: the caller's own pointers and
+// stream, finish() hands the launch's code back -- no HIP call, nothing allocated.  RTBHIP_MEM_HOST: device blocks from the cache of
+// hostpipe.cpp (inputs uploaded), the NULL stream; finish() waits for the device and copies the outputs back in the order they were named.
 // The high-volume calls -- fkine / jacob / fkine_jacob / hessian and rne -- go through host_pipeline instead.
-struct Staging {
-    std::vector<void *> bufs;
-    ~Staging() { for (void *p : bufs) dev_cache_free(p); }
-    int in(const void *host, size_t bytes, void **dev)
+class Staged {
+    struct Buf { void *host, *dev; size_t bytes; };
+    const bool host_;
+    const hipStream_t stream_;
+    int rc_ = RTBHIP_OK;
+    std::vector<Buf> bufs_;               // host mode only; outputs have host != NULL
+
+    int stage(const void *host, size_t bytes, void **dev, void *fetch_to)
     {
-        *dev = nullptr;
-        if (host == nullptr || bytes == 0) return RTBHIP_OK;
-        RTB_TRY_(dev_cache_alloc(bytes, dev));
-        bufs.push_back(*dev);
-        RTB_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+        RTB_TRY(dev_cache_alloc(bytes, dev));
+        bufs_.push_back({fetch_to, *dev, bytes});
+        if (host) RTB_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
         return RTBHIP_OK;
     }
-    int out(size_t bytes, void **dev)
+    void *add(const void *in_from, void *fetch_to, size_t bytes)
     {
-        *dev = nullptr;
-        if (bytes == 0) return RTBHIP_OK;
-        RTB_TRY_(dev_cache_alloc(bytes, dev));
-        bufs.push_back(*dev);
+        void *dev = nullptr;
+        if (rc_ == RTBHIP_OK) rc_ = stage(in_from, bytes, &dev, fetch_to);
+        return rc_ == RTBHIP_OK ? dev : nullptr;
+    }
+    int fetch_all()
+    {
+        RTB_HIP(hipDeviceSynchronize());
+        for (const Buf &b : bufs_) {
+            void *host = b.host;
+            const void *dev = b.dev;
+            const size_t bytes = b.bytes;
+            if (host) RTB_HIP(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+        }
         return RTBHIP_OK;
     }
+
+public:
+    Staged(int mem, void *stream) : host_(mem == RTBHIP_MEM_HOST), stream_(host_ ? nullptr : (hipStream_t)stream) {}
+    ~Staged() { for (const Buf &b : bufs_) dev_cache_free(b.dev); }
+    Staged(const Staged &) = delete;
+    // the pointer the launcher reads / writes; host mode: NULL for a NULL array or zero bytes
+    template <class T> const T *in(const T *p, size_t bytes) { return !host_ ? p : (p && bytes) ? (const T *)add(p, nullptr, bytes) : nullptr; }
+    template <class T> T *out(T *p, size_t bytes) { return !host_ ? p : (p && bytes) ? (T *)add(nullptr, p, bytes) : nullptr; }
+    hipStream_t stream() const { return stream_; }
+    int status() const { return rc_; }    // of in() / out(): look at it before launching
+    int finish(int launch_rc) { return (!host_ || launch_rc != RTBHIP_OK) ? launch_rc : fetch_all(); }
 };
-#define RTB_TRY(expr)                   \
-    do {                                \
-        int _rc = (expr);               \
-        if (_rc != RTBHIP_OK) return _rc; \
-    } while (0)
 
-static int fetch(void *host, const void *dev, size_t bytes)
-{
-    if (host == nullptr || bytes == 0) return RTBHIP_OK;
-    RTB_HIP(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
-    return RTBHIP_OK;
-}
-
-static Affine affine_from16(const double *m16)
+Affine affine_from16(const double *m16)
 {
     Affine a;
     a.used = m16 != nullptr;
@@ -268,6 +319,7 @@ static Affine affine_from16(const double *m16)
     return a;
 }
 
+// ---------------------------------------------------------------- argument checks shared by the entry families
 // The device a device-pointer call runs on.  The caller's buffers decide: when they live on a GPU other than the current one
 // (a tensor on cuda:1 while device 0 is current -- a single process driving several GPUs) the call switches to that GPU for its
 // duration -- table look-up / upload, launch geometry and the launch itself all happen there -- and the destructor restores the
@@ -292,141 +344,352 @@ struct DeviceScope {
     }
 };
 
-static int check_batch(const char *fn, const void *q, int64_t N, int mem, DeviceScope *scope)
+int refuse(const char *fn, const char *why, int rc = RTBHIP_EINVAL)
 {
-    if (N < 0) { set_error(std::string(fn) + ": negative N"); return RTBHIP_EINVAL; }
-    if (N > 0 && q == nullptr) { set_error(std::string(fn) + ": NULL input with N > 0"); return RTBHIP_EINVAL; }
-    if (mem != RTBHIP_MEM_HOST && mem != RTBHIP_MEM_DEVICE) { set_error(std::string(fn) + ": bad mem kind"); return RTBHIP_EINVAL; }
+    set_error(std::string(fn) + ": " + why);
+    return rc;
+}
+
+int check_mem(const char *fn, int mem)
+{
+    return mem != RTBHIP_MEM_HOST && mem != RTBHIP_MEM_DEVICE ? refuse(fn, "bad mem kind") : RTBHIP_OK;
+}
+
+int check_batch(const char *fn, const void *q, int64_t N, int mem, DeviceScope *scope)
+{
+    if (N < 0) return refuse(fn, "negative N");
+    if (N > 0 && q == nullptr) return refuse(fn, "NULL input with N > 0");
+    RTB_TRY(check_mem(fn, mem));
     if (mem == RTBHIP_MEM_DEVICE && N > 0 && scope) return scope->enter_for(fn, q);
     return RTBHIP_OK;
 }
 
-static int kin_entry(const char *fn, rtbhip_chain_t h, const double *q, int64_t N, const double *base16,
-                     const double *tool16, int frame, double *T, double *J, double *H, int mem, void *stream)
-{
-    const std::shared_ptr<Chain> c_owner = chain_from_handle(h);
-    Chain *c = c_owner.get();
-    RTB_TRACE((std::string("rtbhip_") + fn).c_str());
-    if (!c) { set_error(std::string(fn) + ": unknown chain handle"); return RTBHIP_EINVAL; }
-    DeviceScope dscope;
-    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
-    if (frame != 0 && frame != 1) { set_error(std::string(fn) + ": frame must be 0 (jacob0) or 1 (jacobe)"); return RTBHIP_EINVAL; }
-    if (N > 0 && !T && !J && !H) { set_error(std::string(fn) + ": no output buffer"); return RTBHIP_EINVAL; }
-    if (N == 0) return RTBHIP_OK;
-    if (c->n == 0) {                  // a chain of constants: J is (N, 6, 0) and H (N, 0, 6, 0) -- nothing to write (the reference returns empty arrays)
-        J = nullptr; H = nullptr;
-        if (!T) return RTBHIP_OK;
-    }
-    DevChain ops;
-    RTB_TRY(chain_device_ops(c, &ops, nullptr));
-    Affine base = affine_from16(base16), tool = affine_from16(tool16);
-    const size_t n = (size_t)c->n, qw = (size_t)c->q_width;
-    if (mem == RTBHIP_MEM_DEVICE)
-        return launch_kin(c, ops, q, N, base, tool, frame, T, J, H, (hipStream_t)stream);
-    // host arrays: rows stream through the two-slot pipeline (hostpipe.cpp); the functor sees device copies of one chunk
-    HostIO io;
-    io.add_in(q, qw * 8);
-    io.add_out(T, 128);
-    io.add_out(J, 48 * n);
-    io.add_out(H, 48 * n * n);
-    return host_pipeline(io, N, [&](const void *const *din, void *const *dout, int64_t, int64_t rows, hipStream_t s) {
-        return launch_kin(c, ops, (const double *)din[0], rows, base, tool, frame, (double *)dout[0], (double *)dout[1], (double *)dout[2], s);
-    });
-}
-
-// rtbhip_fkine_jacob_packed: as kin_entry for (T, J), but one (N, 16 + 6n) output array
-static int kin_packed_entry(rtbhip_chain_t h, const double *q, int64_t N, const double *base16, const double *tool16, int frame, double *TJ,
-                            int mem, void *stream)
-{
-    const char *fn = "fkine_jacob_packed";
-    const std::shared_ptr<Chain> c_owner = chain_from_handle(h);
-    Chain *c = c_owner.get();
-    RTB_TRACE("rtbhip_fkine_jacob_packed");
-    if (!c) { set_error(std::string(fn) + ": unknown chain handle"); return RTBHIP_EINVAL; }
-    DeviceScope dscope;
-    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
-    if (frame != 0 && frame != 1) { set_error(std::string(fn) + ": frame must be 0 (jacob0) or 1 (jacobe)"); return RTBHIP_EINVAL; }
-    if (N > 0 && !TJ) { set_error(std::string(fn) + ": no output buffer"); return RTBHIP_EINVAL; }
-    if (N == 0) return RTBHIP_OK;
-    DevChain ops;
-    RTB_TRY(chain_device_ops(c, &ops, nullptr));
-    Affine base = affine_from16(base16), tool = affine_from16(tool16);
-    const size_t n = (size_t)c->n, qw = (size_t)c->q_width;
-    if (c->n == 0) {                  // a chain of constants: the row is the pose alone, (N, 16) -- the plain fkine kernel writes exactly that
-        if (mem == RTBHIP_MEM_DEVICE) return launch_kin(c, ops, q, N, base, tool, frame, TJ, nullptr, nullptr, (hipStream_t)stream);
-        HostIO io0;
-        io0.add_in(q, qw * 8);
-        io0.add_out(TJ, 128);
-        return host_pipeline(io0, N, [&](const void *const *din, void *const *dout, int64_t, int64_t rows, hipStream_t s) {
-            return launch_kin(c, ops, (const double *)din[0], rows, base, tool, frame, (double *)dout[0], nullptr, nullptr, s);
-        });
-    }
-    if (mem == RTBHIP_MEM_DEVICE)
-        return launch_kin_packed(c, ops, q, N, base, tool, frame, TJ, (hipStream_t)stream);
-    HostIO io;
-    io.add_in(q, qw * 8);
-    io.add_out(TJ, 128 + 48 * n);
-    return host_pipeline(io, N, [&](const void *const *din, void *const *dout, int64_t, int64_t rows, hipStream_t s) {
-        return launch_kin_packed(c, ops, (const double *)din[0], rows, base, tool, frame, (double *)dout[0], s);
-    });
-}
-
-
-// ---- float32 device rows (rtbhip_fkine_jacob_f32, rtbhip_fkine_jacob_packed_f32, rtbhip_rne_f32): the validation of the fp64 entries; host
+// float32 rows (rtbhip_fkine_jacob_f32, rtbhip_fkine_jacob_packed_f32, rtbhip_rne_f32) share the validation of the fp64 entries; host
 // pointers are refused -- the host path converts nothing and is bound by the PCIe link, not by the width of a row (hostpipe.cpp is fp64 only)
-static int check_f32_device(const char *fn, int mem)
+template <class R> int check_row_type(const char *fn, int mem)
 {
-    if (mem == RTBHIP_MEM_HOST) { set_error(std::string(fn) + ": float32 rows are served in device memory only (mem must be RTBHIP_MEM_DEVICE)"); return RTBHIP_EINVAL; }
+    if (std::is_same<R, float>::value && mem == RTBHIP_MEM_HOST) return refuse(fn, "float32 rows are served in device memory only (mem must be RTBHIP_MEM_DEVICE)");
     return RTBHIP_OK;
 }
 
-static int kin_entry_f32(const char *fn, rtbhip_chain_t h, const float *q, int64_t N, const double *base16, const double *tool16, int frame,
-                         float *T, float *J, float *TJ, bool packed, int mem, void *stream)
+bool misaligned16(const void *a, const void *b, const void *c = nullptr) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) != 0; }
+constexpr const char *kAlign16 = "device buffers must be 16-byte aligned";
+
+// ---------------------------------------------------------------- kinematics: fkine / jacob / hessian in any combination, or one packed [T | J] row
+// fp64 rows: device pointers, or host arrays streamed through the two-slot pipeline (hostpipe.cpp) -- the same functor either way, applied to
+// the caller's pointers or to device copies of one chunk
+int kin_run(const Chain *c, const DevChain &ops, const double *q, int64_t N, const Affine &base, const Affine &tool, int frame, double *T, double *J,
+            double *H, double *TJ, int mem, void *stream)
+{
+    const size_t n = (size_t)c->n;
+    HostIO io;
+    io.add_in(q, (size_t)c->q_width * 8);
+    if (TJ) {
+        io.add_out(TJ, 128 + 48 * n);
+    } else {
+        io.add_out(T, 128);
+        io.add_out(J, 48 * n);
+        io.add_out(H, 48 * n * n);
+    }
+    auto launch = [&](const void *const *din, void *const *dout, int64_t, int64_t rows, hipStream_t s) {
+        if (TJ) return launch_kin_packed(c, ops, (const double *)din[0], rows, base, tool, frame, (double *)dout[0], s);
+        return launch_kin(c, ops, (const double *)din[0], rows, base, tool, frame, (double *)dout[0], (double *)dout[1], (double *)dout[2], s);
+    };
+    if (mem == RTBHIP_MEM_DEVICE) return launch(io.in, io.out, 0, N, (hipStream_t)stream);
+    return host_pipeline(io, N, launch);
+}
+
+int kin_run(const Chain *c, const DevChain &ops, const float *q, int64_t N, const Affine &base, const Affine &tool, int frame, float *T, float *J,
+            float *, float *TJ, int, void *stream)
+{
+    if (TJ) return launch_kin_packed_f32(c, ops, q, N, base, tool, frame, TJ, (hipStream_t)stream);
+    return launch_kin_f32(c, ops, q, N, base, tool, frame, T, J, (hipStream_t)stream);
+}
+
+template <class R>
+int kin_entry(const char *fn, rtbhip_chain_t h, const R *q, int64_t N, const double *base16, const double *tool16, int frame, R *T, R *J, R *H, R *TJ,
+              int mem, void *stream)
 {
     const std::shared_ptr<Chain> c_owner = chain_from_handle(h);
     Chain *c = c_owner.get();
-    RTB_TRACE((std::string("rtbhip_") + fn).c_str());
-    if (!c) { set_error(std::string(fn) + ": unknown chain handle"); return RTBHIP_EINVAL; }
+    RTB_TRACE(fn);
+    if (!c) return refuse(fn, "unknown chain handle");
     DeviceScope dscope;
     RTB_TRY(check_batch(fn, q, N, mem, &dscope));
-    RTB_TRY(check_f32_device(fn, mem));
-    if (frame != 0 && frame != 1) { set_error(std::string(fn) + ": frame must be 0 (jacob0) or 1 (jacobe)"); return RTBHIP_EINVAL; }
-    if (N > 0 && !T && !J && !TJ) { set_error(std::string(fn) + ": no output buffer"); return RTBHIP_EINVAL; }
+    RTB_TRY(check_row_type<R>(fn, mem));
+    if (frame != 0 && frame != 1) return refuse(fn, "frame must be 0 (jacob0) or 1 (jacobe)");
+    if (N > 0 && !T && !J && !H && !TJ) return refuse(fn, "no output buffer");
     if (N == 0) return RTBHIP_OK;
-    if (c->n == 0) {                  // a chain of constants: J is (N, 6, 0), a packed row the pose alone (as the fp64 entries)
-        J = nullptr;
-        if (packed) { T = TJ; packed = false; }
+    if (c->n == 0) {                  // a chain of constants: J is (N, 6, 0) and H (N, 0, 6, 0) -- nothing to write (the reference returns empty
+        J = nullptr; H = nullptr;     // arrays) -- and a packed row is the pose alone, (N, 16): what the plain fkine kernel writes
+        if (TJ) { T = TJ; TJ = nullptr; }
         if (!T) return RTBHIP_OK;
     }
     DevChain ops;
     RTB_TRY(chain_device_ops(c, &ops, nullptr));
-    Affine base = affine_from16(base16), tool = affine_from16(tool16);
-    if (packed) return launch_kin_packed_f32(c, ops, q, N, base, tool, frame, TJ, (hipStream_t)stream);
-    return launch_kin_f32(c, ops, q, N, base, tool, frame, T, J, (hipStream_t)stream);
+    return kin_run(c, ops, q, N, affine_from16(base16), affine_from16(tool16), frame, T, J, H, TJ, mem, stream);
 }
 
-void kin_tune(const char *key, int value);
-void rne_tune(const char *key, int value);
-void ik_tune(const char *key, int value);
-void partial_tune(const char *key, int value);
-void ik_release_device_state();
-int ik_prepare_device();
-void hostpipe_tune(const char *key, int value);
-void shard_tune(const char *key, int value);
-void tree_tune(const char *key, int value);
-std::string tree_jit_knowledge(const Tree *t, std::string *type_name);      // tree_kernels.hip
-bool tree_jit_applies(const Tree *t);
+/* Robot.manipulability(J=...) / Robot.jacobm(J=..., H=...) (robot/Robot.py:701-905, :1101-1235): pure functions of the supplied arrays */
+int diff_from_jac_entry(const char *fn, int mode, const double *J, const double *H, int64_t N, int32_t n, int32_t axes, double *out,
+                        int32_t mem, void *stream)
+{
+    if (n < 1 || n > 16) return refuse(fn, "n must be 1..16", RTBHIP_ELIMIT);
+    if ((axes & 63) == 0) return refuse(fn, "empty axes mask");
+    if (N > 0 && !out) return refuse(fn, "NULL output");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, J, N, mem, &dscope));
+    if (N == 0) return RTBHIP_OK;
+    if (mem == RTBHIP_MEM_DEVICE && misaligned16(J, H)) return refuse(fn, kAlign16);
+    Staged st(mem, stream);
+    const size_t jb = (size_t)N * 48 * n;
+    const double *dJ = st.in(J, jb), *dH = st.in(H, jb * n);
+    double *dout = st.out(out, (size_t)N * 8 * (mode == 0 ? 1 : n));
+    RTB_TRY(st.status());
+    return st.finish(launch_diff_from_jac(mode, n, dJ, dH, N, axes, dout, st.stream()));
+}
+
+/* fknm.Angle_Axis (core/fknm.cpp:112-162 -> _angle_axis core/ik.cpp:241-286) and tools/p_servo.py:46-117, batched with broadcasting: what they
+   check alike.  *N = 0: an empty batch, nothing to do.  `gain_ok` sits where rtbhip_p_servo looks at its gain vector. */
+int check_pose_pair(const char *fn, const void *Te, int64_t nTe, const void *Tep, int64_t nTep, bool gain_ok, const void *out, const void *out2,
+                    int mem, DeviceScope *scope, int64_t *N)
+{
+    *N = 0;
+    RTB_TRY(check_mem(fn, mem));
+    if (nTe < 0 || nTep < 0) return refuse(fn, "negative count");
+    if (!gain_ok) return refuse(fn, "NULL gain");
+    if (nTe == 0 || nTep == 0) return RTBHIP_OK;
+    const int64_t n = nTe > nTep ? nTe : nTep;
+    if ((nTe != n && nTe != 1) || (nTep != n && nTep != 1)) return refuse(fn, "the pose counts must be equal, or one of them 1");
+    if (!Te || !Tep || !out || !out2) return refuse(fn, "NULL buffer");
+    if (mem == RTBHIP_MEM_DEVICE) {
+        if (misaligned16(Te, Tep, out)) return refuse(fn, kAlign16);
+        RTB_TRY(scope->enter_for(fn, out));
+    }
+    *N = n;
+    return RTBHIP_OK;
+}
+
+// (rtbhip_p_servo_error reports under the name of rtbhip_angle_axis, whose body it shares)
+int pose_error_entry(const double *Te, int64_t nTe, const double *Tep, int64_t nTep, int method, double *e, int32_t mem, void *stream)
+{
+    DeviceScope dscope;
+    int64_t N;
+    RTB_TRY(check_pose_pair("angle_axis", Te, nTe, Tep, nTep, true, e, e, mem, &dscope, &N));
+    if (N == 0) return RTBHIP_OK;
+    Staged st(mem, stream);
+    const double *dA = st.in(Te, (size_t)nTe * 128), *dB = st.in(Tep, (size_t)nTep * 128);
+    double *dE = st.out(e, (size_t)N * 48);
+    RTB_TRY(st.status());
+    return st.finish(launch_angle_axis(dA, nTe, dB, nTep, N, dE, st.stream(), method));
+}
+
+/* Robot.jacob0_dot / ETS.manipulability (yoshikawa) / ETS.jacobm (SURVEY 8f-4) */
+int diff_entry(const char *fn, rtbhip_chain_t h, int mode, int axes, const double *q, const double *qd, int64_t N,
+               const double *tool16, int frame, double *out, int mem, void *stream)
+{
+    const std::shared_ptr<Chain> c_owner = chain_from_handle(h);
+    Chain *c = c_owner.get();
+    RTB_TRACE(fn);
+    if (!c) return refuse(fn, "unknown chain handle");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    if (frame != 0 && frame != 1) return refuse(fn, "frame must be 0 or 1");
+    if (mode != 0 && mode != 3 && mode != 4 && (axes & 63) == 0) return refuse(fn, "empty axes mask");
+    const bool needs_qd = mode == 0 || mode == 4;
+    if (N > 0 && (!out || (needs_qd && !qd))) return refuse(fn, "NULL qd/output");
+    if (N == 0) return RTBHIP_OK;
+    DevChain ops;
+    RTB_TRY(chain_device_ops(c, &ops, nullptr));
+    const size_t n = (size_t)c->n, qbytes = (size_t)N * c->q_width * 8;
+    Staged st(mem, stream);
+    const double *dq = st.in(q, qbytes), *dqd = st.in(qd, needs_qd ? qbytes : 0);
+    double *dout = st.out(out, (size_t)N * 8 * ((mode == 0 || mode == 3 || mode == 4) ? 6 * n : (mode == 1 ? 1 : n)));
+    RTB_TRY(st.status());
+    return st.finish(launch_kin_diff(c, ops, mode, axes, dq, dqd, N, affine_from16(tool16), frame, dout, st.stream()));
+}
+
+// restart-generator key of row 0 for the IK calls this thread makes from now on (rtbhip.h)
+thread_local int64_t t_ik_target_base = 0;
+
+// rtbhip_ik_lm / rtbhip_ik_lm_nullspace / rtbhip_ik_qp (method 5: kj travels in lambda)
+int ik_entry(rtbhip_chain_t chain, const double *Tep, int64_t N, const double *q0,
+             int32_t ilimit, int32_t slimit, double tol, int32_t reject_jl, const double *we6,
+             double lambda, int32_t method, int32_t flavour, uint64_t seed,
+             double kq, double km, double ps, const double *pi, double ks, double *q_out,
+             int32_t *success, int32_t *iters, int32_t *searches, double *residual,
+             int32_t mem, void *stream)
+{
+    const char *fn = "ik_lm";
+    const std::shared_ptr<Chain> c_owner = chain_from_handle(chain);
+    Chain *c = c_owner.get();
+    RTB_TRACE(fn);
+    if (!c) return refuse(fn, "unknown chain handle");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, Tep, N, mem, &dscope));
+    if (flavour < 0 || flavour > 1) return refuse(fn, "flavour must be 0 (ik_LM) or 1 (ikine_LM)");
+    if (ilimit < 1 || slimit < 1) return refuse(fn, "ilimit and slimit must be >= 1");
+    if (c->n < 1) return refuse(fn, "chain has no joints");
+    if (c->q_width != c->n) return refuse(fn, "chain must use jindex 0..n-1 (reference ik.cpp:34-37 assumes the same)");
+    if (N > 0 && (!q_out || !success || !iters || !searches || !residual)) return refuse(fn, "NULL output");
+    if (N == 0) return RTBHIP_OK;
+    IkParams p;
+    p.ilimit = ilimit; p.slimit = slimit; p.reject_jl = reject_jl ? 1 : 0; p.method = method;
+    p.flavour = flavour; p.tol = tol; p.lambda = lambda; p.seed = seed;
+    p.kq = kq; p.km = km; p.ps = ps; p.ks = ks; p.target0 = t_ik_target_base;
+    for (int j = 0; j < RTBHIP_MAX_JOINTS; ++j) p.pi[j] = pi ? pi[j < c->n ? j : (c->n > 0 ? c->n - 1 : 0)] : 0.3;      // NULL: the reference's default
+    if (kq > 0.0 && flavour != 1) return refuse(fn, "null-space terms belong to the Python solvers (flavour 1)");
+    if (kq > 0.0)
+        for (int j = 0; j < c->n && j < RTBHIP_MAX_JOINTS; ++j)
+            if (ps == p.pi[j]) return refuse(fn, "ps must differ from pi");
+    for (int i = 0; i < 6; i++) p.we[i] = we6 ? we6[i] : 1.0;
+    RTB_TRY(ik_check_limits(c, p, N));                 // what the device build refuses, before the device is touched
+    DevChain ops;
+    const double *qlim = nullptr;
+    RTB_TRY(chain_device_ops(c, &ops, &qlim));
+    const size_t rows = (size_t)N, qbytes = rows * (size_t)c->n * 8;
+    Staged st(mem, stream);
+    const double *dTep = st.in(Tep, rows * 128), *dq0 = st.in(q0, qbytes);
+    double *dq = st.out(q_out, qbytes);
+    int32_t *ds = st.out(success, rows * 4), *di = st.out(iters, rows * 4), *dse = st.out(searches, rows * 4);
+    double *dr = st.out(residual, rows * 8);
+    RTB_TRY(st.status());
+    return st.finish(launch_ik(c, ops, qlim, dTep, N, dq0, p, dq, ds, di, dse, dr, st.stream()));
+}
+
+// ---------------------------------------------------------------- dynamics
+// rtbhip_rne / rtbhip_rne_base_wrench: device pointers or the host pipeline, one functor; rtbhip_rne_f32: device rows only, no base wrench
+int rne_run(const Dyn *d, const DevLink *links, const double *q, const double *qd, const double *qdd, int64_t N, const double *grav3,
+            const double *fext6, double *tau, double *wbase, bool want_wbase, int mem, void *stream)
+{
+    HostIO io;
+    const size_t row = (size_t)d->n * 8;
+    io.add_in(q, row); io.add_in(qd, row); io.add_in(qdd, row);          // qd / qdd may be NULL (= zeros): skipped, not staged
+    io.add_out(tau, row);
+    if (want_wbase) io.add_out(wbase, 6 * 8);
+    auto launch = [&](const void *const *din, void *const *dout, int64_t, int64_t rows, hipStream_t s) {
+        return launch_rne(d, links, (const double *)din[0], (const double *)din[1], (const double *)din[2], rows, grav3, fext6, (double *)dout[0], s,
+                          want_wbase ? (double *)dout[1] : nullptr);
+    };
+    if (mem == RTBHIP_MEM_DEVICE) return launch(io.in, io.out, 0, N, (hipStream_t)stream);
+    return host_pipeline(io, N, launch);
+}
+
+int rne_run(const Dyn *d, const DevLink *links, const float *q, const float *qd, const float *qdd, int64_t N, const double *grav3,
+            const double *fext6, float *tau, float *, bool, int, void *stream)
+{
+    return launch_rne_f32(d, links, q, qd, qdd, N, grav3, fext6, tau, (hipStream_t)stream);
+}
+
+template <class R>
+int rne_entry(const char *fn, rtbhip_dyn_t dyn, const R *q, const R *qd, const R *qdd, int64_t N, const double *grav3, const double *fext6, R *tau,
+              R *wbase, bool want_wbase, int32_t mem, void *stream)
+{
+    RTB_TRACE(fn);
+    const std::shared_ptr<Dyn> d_owner = dyn_from_handle(dyn);
+    Dyn *d = d_owner.get();
+    if (!d) return refuse(fn, "unknown dyn handle");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    RTB_TRY(check_row_type<R>(fn, mem));
+    if (!grav3) return refuse(fn, "NULL gravity");
+    if (N > 0 && !tau) return refuse(fn, "NULL tau");   // qd / qdd may be NULL (= zeros)
+    if (want_wbase && N > 0 && !wbase) return refuse(fn, "NULL wbase");
+    if (N == 0) return RTBHIP_OK;
+    const DevLink *links = nullptr;
+    RTB_TRY(dyn_device_links(d, &links));
+    return rne_run(d, links, q, qd, qdd, N, grav3, fext6, tau, wbase, want_wbase, mem, stream);
+}
+
+/* Dynamics.inertia / coriolis / accel (robot/Dynamics.py:704-861, 424-509) of a DH arm (kind "dyn": dyn_from_handle, dyn_device_links,
+   launch_dyn) and of an ETS robot's link tree over Robot.rne (kind "tree").  mode: 0 inertia, 1 coriolis, 2 accel. */
+template <class Obj, class Table>
+int dyn_terms_entry(const char *fn, const char *kind, const std::shared_ptr<Obj> owner, int (*table_of)(Obj *, const Table **),
+                    int (*launch)(const Obj *, const Table *, int, const double *, const double *, const double *, int64_t, const double *, double *, hipStream_t),
+                    int mode, const double *q, const double *qd, const double *tq, int64_t N, const double *grav3, double *out, int32_t mem, void *stream)
+{
+    Obj *d = owner.get();
+    RTB_TRACE(fn);
+    if (!d) return refuse(fn, (std::string("unknown ") + kind + " handle").c_str());
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    if (N > 0 && !out) return refuse(fn, "NULL output");
+    if (N > 0 && mode >= 1 && !qd) return refuse(fn, "NULL qd");
+    if (N > 0 && mode == 2 && (!tq || !grav3)) return refuse(fn, "NULL torque/gravity");
+    if (N == 0) return RTBHIP_OK;
+    const Table *table = nullptr;
+    RTB_TRY(table_of(d, &table));
+    const size_t n = (size_t)d->n, bytes = (size_t)N * n * 8;
+    Staged st(mem, stream);
+    const double *dq = st.in(q, bytes), *dqd = st.in(qd, mode >= 1 ? bytes : 0), *dtq = st.in(tq, mode == 2 ? bytes : 0);
+    double *dout = st.out(out, mode == 2 ? bytes : bytes * n);
+    RTB_TRY(st.status());
+    return st.finish(launch(d, table, mode, dq, dqd, dtq, N, grav3, dout, st.stream()));
+}
+
+int dyn_entry(const char *fn, rtbhip_dyn_t dyn, int mode, const double *q, const double *qd, const double *tq, int64_t N, const double *grav3,
+              double *out, int32_t mem, void *stream)
+{
+    return dyn_terms_entry(fn, "dyn", dyn_from_handle(dyn), dyn_device_links, launch_dyn, mode, q, qd, tq, N, grav3, out, mem, stream);
+}
+
+int tree_dyn_entry(const char *fn, rtbhip_tree_t tree, int mode, const double *q, const double *qd, const double *tq, int64_t N, const double *grav3,
+                   double *out, int32_t mem, void *stream)
+{
+    return dyn_terms_entry(fn, "tree", tree_from_handle(tree), tree_device_groups, launch_tree_dyn, mode, q, qd, tq, N, grav3, out, mem, stream);
+}
+
+// ---------------------------------------------------------------- a fleet: several chains, each with its own batch, one launch
+int fleet_entry(const rtbhip_chain_t *chains, int32_t n_chains, const double *const *q,
+                const int64_t *N, int32_t frame, double *const *T, double *const *J,
+                int32_t mem, void *stream, bool packed)
+{
+    // packed: T[c] is the (N[c], 16 + 6 n_c) array of [T | J] rows, J is not used
+    if (n_chains < 0 || (n_chains > 0 && (!chains || !q || !N || !T || (!packed && !J)))) { set_error("fleet: bad argument"); return RTBHIP_EINVAL; }
+    RTB_TRACE(packed ? "fleet_fkine_jacob_packed" : "fleet_fkine_jacob");
+    if (frame != 0 && frame != 1) return refuse("fleet", "frame must be 0 or 1");
+    RTB_TRY(check_mem("fleet", mem));
+    std::vector<FleetEntry> entries;
+    Staged st(mem, stream);
+    DeviceScope dscope;
+    if (mem == RTBHIP_MEM_DEVICE)
+        for (int i = 0; i < n_chains; i++)
+            if (N[i] > 0 && q[i]) { RTB_TRY(dscope.enter_for("fleet", q[i])); break; }
+    int64_t tile0 = 0;
+    for (int i = 0; i < n_chains; i++) {
+        const std::shared_ptr<Chain> c_owner = chain_from_handle(chains[i]);
+        Chain *c = c_owner.get();
+        if (!c) return refuse("fleet", "unknown chain handle");
+        if (N[i] < 0) return refuse("fleet", "negative N");
+        if (N[i] == 0) continue;
+        if (!q[i] || !T[i] || (!packed && !J[i])) return refuse("fleet", "NULL buffer");
+        FleetEntry e;
+        RTB_TRY(chain_device_ops(c, &e.dc, nullptr));
+        e.n = c->n; e.q_width = c->q_width; e.N = N[i]; e.tile0 = tile0;
+        e.stride = 0; e.pad = 0;
+        const size_t rows = (size_t)N[i], jbytes = rows * 48 * c->n;
+        e.q = st.in(q[i], rows * c->q_width * 8);
+        e.T = st.out(T[i], packed ? rows * 128 + jbytes : rows * 128);
+        e.J = packed ? nullptr : st.out(J[i], jbytes);
+        RTB_TRY(st.status());
+        tile0 += (N[i] + 63) / 64;
+        entries.push_back(e);
+    }
+    if (entries.empty()) return RTBHIP_OK;
+    return st.finish(launch_fleet(entries, frame, st.stream(), packed));
+}
+
 // ask for a handle's run-time instantiations (jit.cpp).  At *_create: the kernels a first call is most likely to want; all = every variant.
-static void jit_request_chain(const Chain *c, bool touch)
+void jit_request_chain(const Chain *c, bool touch)
 {
     for (const std::string &e : ik_jit_names(c)) jit_request("ik_kernels.hip", e, std::string(), touch);
 }
-static void jit_request_dyn(const Dyn *d, bool all, bool touch)
+void jit_request_dyn(const Dyn *d, bool all, bool touch)
 {
     const std::vector<std::string> nm = rne_jit_names(d);          // k_rne, k_rne_atrest, k_dyn x 3
     for (size_t i = 0; i < nm.size() && (all || i < 2); ++i) jit_request(i < 2 ? "rne_kernels.hip" : "dyn_kernels.hip", nm[i], std::string(), touch);
 }
-static void jit_request_tree(const Tree *t, bool all, bool touch)
+void jit_request_tree(const Tree *t, bool all, bool touch)
 {
     const std::vector<std::string> nm = tree_jit_names(t);         // k_tree_rne (+ at rest), k_tree_dyn x 3
     if (nm.empty()) return;
@@ -436,6 +699,34 @@ static void jit_request_tree(const Tree *t, bool all, bool touch)
         jit_request(nm[i].find("k_tree_dyn") != std::string::npos ? "tree_dyn_kernels.hip" : "tree_kernels.hip", nm[i], pre, touch);
 }
 
+// Make a handle's device table resident on `device` (-1: the current one) NOW: after this returns, device-pointer calls with the
+// handle on that device only enqueue kernels -- no allocation, no synchronous copy -- so they can be captured into a hipGraph
+// without a warm-up call.
+int upload_on(int32_t device, const std::function<int()> &fn)
+{
+    int cur = 0;
+    RTB_HIP(hipGetDevice(&cur));
+    int have = 0;
+    RTB_HIP(hipGetDeviceCount(&have));
+    if (device < -1 || device >= have) { set_error("upload: no such device"); return RTBHIP_EINVAL; }
+    const bool sw = device >= 0 && device != cur;
+    if (sw) RTB_HIP(hipSetDevice(device));
+    const int rc = fn();
+    if (sw) (void)hipSetDevice(cur);
+    return rc;
+}
+
+void trim_default_pool(size_t keep_bytes)      // the stream-ordered temporaries' pool (pool_keep_cached)
+{
+    int dev = 0;
+    hipMemPool_t pool;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess) (void)hipMemPoolTrimTo(pool, keep_bytes);
+    else (void)hipGetLastError();
+}
+
+int g_rne_pszero = 1;      // rtbhip_tune("rne_pszero", 0): handles created afterwards do not take the p* = 0 shortcut (A/B; same values)
+
+}  // namespace
 }  // namespace rtbhip
 
 using namespace rtbhip;
@@ -456,32 +747,15 @@ int rtbhip_init(int32_t n_devices)
 
 void rtbhip_shutdown(void)
 {
-    // device copies of every table are dropped (handles stay valid: tables are re-uploaded lazily on next use)
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    for (auto &kv : g_chains) {
-        std::lock_guard<std::mutex> l2(kv.second->mu);
-        for (auto &d : kv.second->dev_ops) (void)hipFree(d.second);
-        for (auto &d : kv.second->dev_qlim) (void)hipFree(d.second);
-        kv.second->dev_ops.clear(); kv.second->dev_qlim.clear();
-    }
-    for (auto &kv : g_dyns) {
-        std::lock_guard<std::mutex> l2(kv.second->mu);
-        for (auto &d : kv.second->dev_links) (void)hipFree(d.second);
-        kv.second->dev_links.clear();
-    }
-    for (auto &kv : g_trees) {
-        std::lock_guard<std::mutex> l2(kv.second->mu);
-        for (auto &d : kv.second->dev_groups) (void)hipFree(d.second);
-        kv.second->dev_groups.clear();
-    }
+    // device copies of every table are dropped (handles stay valid: tables are re-uploaded lazily on next use); one registry at a time, in this order
+    drop_all_device_copies(g_chains);
+    drop_all_device_copies(g_dyns);
+    drop_all_device_copies(g_trees);
     ik_release_device_state();
     hostpipe_release();
     dev_cache_release();
     host_cache_trim(0);
-    // the stream-ordered temporaries of partial_fkine0 stay cached in the device's default pool: hand them back
-    int dev = 0;
-    hipMemPool_t pool;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess) (void)hipMemPoolTrimTo(pool, 0);
+    trim_default_pool(0);      // the stream-ordered temporaries of partial_fkine0 stay cached in the device's default pool: hand them back
 }
 
 int rtbhip_device_count(int *count)
@@ -492,16 +766,15 @@ int rtbhip_device_count(int *count)
     return RTBHIP_OK;
 }
 
+// *_create: the handle's run-time instantiations are asked for (worker thread; nobody waits -- the first launches take the general kernels)
+// BEFORE the registry is locked: the request computes signatures and may load the run-time compiler
 int rtbhip_chain_create(const rtbhip_et *ets, int32_t m, const double *qlim, rtbhip_chain_t *chain)
 {
     if (!chain) { set_error("chain_create: NULL out"); return RTBHIP_EINVAL; }
     std::shared_ptr<Chain> c(new Chain());
     RTB_TRY(compile_chain(ets, m, qlim, c.get()));
-    jit_request_chain(c.get(), false);       // a chain without a built-in k_ik instantiation: ask for its own (worker thread; nobody waits)
-    uint64_t h = g_next.fetch_add(1);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_chains[h] = std::move(c);
-    *chain = h;
+    jit_request_chain(c.get(), false);       // a chain without a built-in k_ik instantiation: its own
+    *chain = g_chains.add(std::move(c));
     return RTBHIP_OK;
 }
 
@@ -511,30 +784,11 @@ int rtbhip_chain_create_poe(const double *twists, int32_t n, const double *T0_16
     std::shared_ptr<Chain> c(new Chain());
     RTB_TRY(compile_poe(twists, n, T0_16, qlim, c.get()));
     jit_request_chain(c.get(), false);
-    uint64_t h = g_next.fetch_add(1);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_chains[h] = std::move(c);
-    *chain = h;
+    *chain = g_chains.add(std::move(c));
     return RTBHIP_OK;
 }
 
-// Make the handle's device table resident on `device` (-1: the current one) NOW: after this returns, device-pointer calls with the
-// handle on that device only enqueue kernels -- no allocation, no synchronous copy -- so they can be captured into a hipGraph
-// without a warm-up call.  Also sizes the per-device scheduler state rtbhip_ik_lm needs.
-static int upload_on(int32_t device, const std::function<int()> &fn)
-{
-    int cur = 0;
-    RTB_HIP(hipGetDevice(&cur));
-    int have = 0;
-    RTB_HIP(hipGetDeviceCount(&have));
-    if (device < -1 || device >= have) { set_error("upload: no such device"); return RTBHIP_EINVAL; }
-    const bool sw = device >= 0 && device != cur;
-    if (sw) RTB_HIP(hipSetDevice(device));
-    const int rc = fn();
-    if (sw) (void)hipSetDevice(cur);
-    return rc;
-}
-
+// rtbhip_chain_upload also sizes the per-device scheduler state rtbhip_ik_lm needs
 int rtbhip_chain_upload(rtbhip_chain_t chain, int32_t device)
 {
     const std::shared_ptr<Chain> c = chain_from_handle(chain);
@@ -566,25 +820,14 @@ int rtbhip_trim(uint64_t keep_device_bytes, uint64_t keep_pinned_bytes)
 {
     dev_cache_trim((size_t)keep_device_bytes);
     host_cache_trim((size_t)keep_pinned_bytes);
-    int dev = 0;
-    hipMemPool_t pool;      // the stream-ordered temporaries' pool (pool_keep_cached)
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess) (void)hipMemPoolTrimTo(pool, (size_t)keep_device_bytes);
-    else (void)hipGetLastError();
+    trim_default_pool((size_t)keep_device_bytes);
     return RTBHIP_OK;
 }
 
-int rtbhip_chain_destroy(rtbhip_chain_t chain)
-{
-    std::shared_ptr<Chain> c;             // the device tables go with the last reference (a launch in flight keeps one)
-    {
-        std::lock_guard<std::mutex> lk(g_reg_mu);
-        auto it = g_chains.find(chain);
-        if (it == g_chains.end()) { set_error("chain_destroy: unknown handle"); return RTBHIP_EINVAL; }
-        c = std::move(it->second);
-        g_chains.erase(it);
-    }
-    return RTBHIP_OK;
-}
+// *_destroy: the device tables go with the last reference (a launch in flight keeps one)
+int rtbhip_chain_destroy(rtbhip_chain_t chain) { return g_chains.destroy(chain, "chain_destroy"); }
+int rtbhip_dyn_destroy(rtbhip_dyn_t dyn) { return g_dyns.destroy(dyn, "dyn_destroy"); }
+int rtbhip_tree_destroy(rtbhip_tree_t tree) { return g_trees.destroy(tree, "tree_destroy"); }
 
 int rtbhip_chain_info(rtbhip_chain_t chain, int32_t *n, int32_t *m, int32_t *q_width)
 {
@@ -616,14 +859,14 @@ int rtbhip_fkine(rtbhip_chain_t chain, const double *q, int64_t N, const double 
                  const double *tool16, double *T, int32_t mem, void *stream)
 {
     if (N > 0 && !T) { set_error("fkine: NULL T"); return RTBHIP_EINVAL; }
-    return kin_entry("fkine", chain, q, N, base16, tool16, 0, T, nullptr, nullptr, mem, stream);
+    return kin_entry<double>("fkine", chain, q, N, base16, tool16, 0, T, nullptr, nullptr, nullptr, mem, stream);
 }
 
 int rtbhip_jacob(rtbhip_chain_t chain, const double *q, int64_t N, const double *tool16,
                  int32_t frame, double *J, int32_t mem, void *stream)
 {
     if (N > 0 && !J) { set_error("jacob: NULL J"); return RTBHIP_EINVAL; }
-    return kin_entry("jacob", chain, q, N, nullptr, tool16, frame, nullptr, J, nullptr, mem, stream);
+    return kin_entry<double>("jacob", chain, q, N, nullptr, tool16, frame, nullptr, J, nullptr, nullptr, mem, stream);
 }
 
 int rtbhip_fkine_jacob(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16,
@@ -631,112 +874,78 @@ int rtbhip_fkine_jacob(rtbhip_chain_t chain, const double *q, int64_t N, const d
                        void *stream)
 {
     if (N > 0 && (!T || !J)) { set_error("fkine_jacob: NULL T or J"); return RTBHIP_EINVAL; }
-    return kin_entry("fkine_jacob", chain, q, N, base16, tool16, frame, T, J, nullptr, mem, stream);
+    return kin_entry<double>("fkine_jacob", chain, q, N, base16, tool16, frame, T, J, nullptr, nullptr, mem, stream);
 }
 
 int rtbhip_fkine_jacob_packed(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16,
                               const double *tool16, int32_t frame, double *TJ, int32_t mem, void *stream)
 {
-    return kin_packed_entry(chain, q, N, base16, tool16, frame, TJ, mem, stream);
+    return kin_entry<double>("fkine_jacob_packed", chain, q, N, base16, tool16, frame, nullptr, nullptr, nullptr, TJ, mem, stream);
 }
 
 int rtbhip_fkine_jacob_f32(rtbhip_chain_t chain, const float *q, int64_t N, const double *base16,
                            const double *tool16, int32_t frame, float *T, float *J, int32_t mem,
                            void *stream)
 {
-    return kin_entry_f32("fkine_jacob_f32", chain, q, N, base16, tool16, frame, T, J, nullptr, false, mem, stream);
+    return kin_entry<float>("fkine_jacob_f32", chain, q, N, base16, tool16, frame, T, J, nullptr, nullptr, mem, stream);
 }
 
 int rtbhip_fkine_jacob_packed_f32(rtbhip_chain_t chain, const float *q, int64_t N, const double *base16,
                                   const double *tool16, int32_t frame, float *TJ, int32_t mem, void *stream)
 {
     if (N > 0 && !TJ) { set_error("fkine_jacob_packed_f32: no output buffer"); return RTBHIP_EINVAL; }
-    return kin_entry_f32("fkine_jacob_packed_f32", chain, q, N, base16, tool16, frame, nullptr, nullptr, TJ, true, mem, stream);
+    return kin_entry<float>("fkine_jacob_packed_f32", chain, q, N, base16, tool16, frame, nullptr, nullptr, nullptr, TJ, mem, stream);
 }
 
 int rtbhip_hessian(rtbhip_chain_t chain, const double *q, int64_t N, const double *tool16,
                    int32_t frame, double *H, int32_t mem, void *stream)
 {
     if (N > 0 && !H) { set_error("hessian: NULL H"); return RTBHIP_EINVAL; }
-    return kin_entry("hessian", chain, q, N, nullptr, tool16, frame, nullptr, nullptr, H, mem, stream);
+    return kin_entry<double>("hessian", chain, q, N, nullptr, tool16, frame, nullptr, nullptr, H, nullptr, mem, stream);
 }
 
 /* ETS_hessian0 / ETS_hessiane with a supplied Jacobian (core/fknm.cpp:583-783 -> _ETS_hessian core/methods.cpp:16-32) */
 int rtbhip_hessian_from_jacobian(const double *J, int64_t N, int32_t n, double *H, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_hessian_from_jacobian");
-    DeviceScope dscope;
-    RTB_TRY(check_batch("hessian_from_jacobian", J, N, mem, &dscope));
-    if (n < 1 || n > RTBHIP_MAX_JOINTS) { set_error("hessian_from_jacobian: n must be 1..RTBHIP_MAX_JOINTS"); return RTBHIP_ELIMIT; }
-    if (N > 0 && !H) { set_error("hessian_from_jacobian: NULL H"); return RTBHIP_EINVAL; }
-    if (N == 0) return RTBHIP_OK;
-    if (mem == RTBHIP_MEM_DEVICE) {
-        if (((uintptr_t)J | (uintptr_t)H) & 15) { set_error("hessian_from_jacobian: device buffers must be 16-byte aligned"); return RTBHIP_EINVAL; }
-        return launch_hess_from_jac(n, J, N, H, (hipStream_t)stream);
-    }
-    Staging st;
-    void *dJ, *dH;
-    const size_t jb = (size_t)N * 48 * n, hb = jb * n;
-    RTB_TRY(st.in(J, jb, &dJ));
-    RTB_TRY(st.out(hb, &dH));
-    RTB_TRY(launch_hess_from_jac(n, (const double *)dJ, N, (double *)dH, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(H, dH, hb));
-    return RTBHIP_OK;
-}
-
-/* Robot.manipulability(J=...) / Robot.jacobm(J=..., H=...) (robot/Robot.py:701-905, :1101-1235): pure functions of the supplied arrays */
-static int diff_from_jac_entry(const char *fn, int mode, const double *J, const double *H, int64_t N, int32_t n, int32_t axes, double *out,
-                               int32_t mem, void *stream)
-{
-    if (n < 1 || n > 16) { set_error(std::string(fn) + ": n must be 1..16"); return RTBHIP_ELIMIT; }
-    if ((axes & 63) == 0) { set_error(std::string(fn) + ": empty axes mask"); return RTBHIP_EINVAL; }
-    if (N > 0 && !out) { set_error(std::string(fn) + ": NULL output"); return RTBHIP_EINVAL; }
+    const char *fn = "hessian_from_jacobian";
+    RTB_TRACE(fn);
     DeviceScope dscope;
     RTB_TRY(check_batch(fn, J, N, mem, &dscope));
+    if (n < 1 || n > RTBHIP_MAX_JOINTS) return refuse(fn, "n must be 1..RTBHIP_MAX_JOINTS", RTBHIP_ELIMIT);
+    if (N > 0 && !H) return refuse(fn, "NULL H");
     if (N == 0) return RTBHIP_OK;
-    if (mem == RTBHIP_MEM_DEVICE) {
-        if (((uintptr_t)J | (uintptr_t)H) & 15) { set_error(std::string(fn) + ": device buffers must be 16-byte aligned"); return RTBHIP_EINVAL; }
-        return launch_diff_from_jac(mode, n, J, H, N, axes, out, (hipStream_t)stream);
-    }
-    Staging st;
-    void *dJ, *dH = nullptr, *dout;
-    const size_t jb = (size_t)N * 48 * n, ob = (size_t)N * 8 * (mode == 0 ? 1 : n);
-    RTB_TRY(st.in(J, jb, &dJ));
-    if (H) RTB_TRY(st.in(H, jb * n, &dH));
-    RTB_TRY(st.out(ob, &dout));
-    RTB_TRY(launch_diff_from_jac(mode, n, (const double *)dJ, (const double *)dH, N, axes, (double *)dout, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(out, dout, ob));
-    return RTBHIP_OK;
+    if (mem == RTBHIP_MEM_DEVICE && misaligned16(J, H)) return refuse(fn, kAlign16);
+    Staged st(mem, stream);
+    const size_t jb = (size_t)N * 48 * n;
+    const double *dJ = st.in(J, jb);
+    double *dH = st.out(H, jb * n);
+    RTB_TRY(st.status());
+    return st.finish(launch_hess_from_jac(n, dJ, N, dH, st.stream()));
 }
 
 int rtbhip_manipulability_from_jacobian(const double *J, int64_t N, int32_t n, int32_t axes_mask, int32_t method, double *m, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_manipulability_from_jacobian");
+    RTB_TRACE("manipulability_from_jacobian");
     if (method < 0 || method > 2) { set_error("manipulability_from_jacobian: method must be 0 yoshikawa, 1 minsingular, 2 invcondition"); return RTBHIP_EINVAL; }
     return diff_from_jac_entry("manipulability_from_jacobian", 0, J, nullptr, N, n, (axes_mask & 63) | (method << 8), m, mem, stream);
 }
 
 int rtbhip_jacobm_from_jacobian(const double *J, const double *H, int64_t N, int32_t n, int32_t axes_mask, double *Jm, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_jacobm_from_jacobian");
+    RTB_TRACE("jacobm_from_jacobian");
     return diff_from_jac_entry("jacobm_from_jacobian", H ? 2 : 1, J, H, N, n, axes_mask & 63, Jm, mem, stream);
 }
 
-/* fknm.Angle_Axis (core/fknm.cpp:112-162 -> _angle_axis core/ik.cpp:241-286), batched with broadcasting */
-static int pose_error_entry(const double *Te, int64_t nTe, const double *Tep, int64_t nTep, int method, double *e, int32_t mem, void *stream);
-
 int rtbhip_angle_axis(const double *Te, int64_t nTe, const double *Tep, int64_t nTep, double *e, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_angle_axis");
+    RTB_TRACE("angle_axis");
     return pose_error_entry(Te, nTe, Tep, nTep, 0, e, mem, stream);
 }
 
 /* the error vector of tools/p_servo.py:46-117: method 0 "angle-axis" (= rtbhip_angle_axis), 1 "rpy" (the reference's default) */
 int rtbhip_p_servo_error(const double *Te, int64_t nTe, const double *Tep, int64_t nTep, int32_t method, double *e, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_p_servo_error");
+    RTB_TRACE("p_servo_error");
     if (method != 0 && method != 1) { set_error("p_servo_error: method must be 0 angle-axis or 1 rpy"); return RTBHIP_EINVAL; }
     return pose_error_entry(Te, nTe, Tep, nTep, method, e, mem, stream);
 }
@@ -745,88 +954,19 @@ int rtbhip_p_servo_error(const double *Te, int64_t nTe, const double *Tep, int64
 int rtbhip_p_servo(const double *Te, int64_t nTe, const double *Tep, int64_t nTep, int32_t method, const double *gain6, double threshold, double *v,
                    uint8_t *arrived, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_p_servo");
-    if (method != 0 && method != 1) { set_error("p_servo: method must be 0 angle-axis or 1 rpy"); return RTBHIP_EINVAL; }
-    if (mem != RTBHIP_MEM_HOST && mem != RTBHIP_MEM_DEVICE) { set_error("p_servo: bad mem kind"); return RTBHIP_EINVAL; }
-    if (nTe < 0 || nTep < 0) { set_error("p_servo: negative count"); return RTBHIP_EINVAL; }
-    if (!gain6) { set_error("p_servo: NULL gain"); return RTBHIP_EINVAL; }
-    if (nTe == 0 || nTep == 0) return RTBHIP_OK;
-    const int64_t N = nTe > nTep ? nTe : nTep;
-    if ((nTe != N && nTe != 1) || (nTep != N && nTep != 1)) { set_error("p_servo: the pose counts must be equal, or one of them 1"); return RTBHIP_EINVAL; }
-    if (!Te || !Tep || !v || !arrived) { set_error("p_servo: NULL buffer"); return RTBHIP_EINVAL; }
-    if (mem == RTBHIP_MEM_DEVICE) {
-        if (((uintptr_t)Te | (uintptr_t)Tep | (uintptr_t)v) & 15) { set_error("p_servo: device buffers must be 16-byte aligned"); return RTBHIP_EINVAL; }
-        DeviceScope dscope;
-        RTB_TRY(dscope.enter_for("p_servo", v));
-        return launch_p_servo(Te, nTe, Tep, nTep, N, method, gain6, threshold, v, arrived, (hipStream_t)stream);
-    }
-    Staging st;
-    void *dA, *dB, *dV, *dF;
-    RTB_TRY(st.in(Te, (size_t)nTe * 128, &dA));
-    RTB_TRY(st.in(Tep, (size_t)nTep * 128, &dB));
-    RTB_TRY(st.out((size_t)N * 48, &dV));
-    RTB_TRY(st.out((size_t)N, &dF));
-    RTB_TRY(launch_p_servo((const double *)dA, nTe, (const double *)dB, nTep, N, method, gain6, threshold, (double *)dV, (unsigned char *)dF, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(v, dV, (size_t)N * 48));
-    return fetch(arrived, dF, (size_t)N);
-}
-
-static int pose_error_entry(const double *Te, int64_t nTe, const double *Tep, int64_t nTep, int method, double *e, int32_t mem, void *stream)
-{
-    if (mem != RTBHIP_MEM_HOST && mem != RTBHIP_MEM_DEVICE) { set_error("angle_axis: bad mem kind"); return RTBHIP_EINVAL; }
-    if (nTe < 0 || nTep < 0) { set_error("angle_axis: negative count"); return RTBHIP_EINVAL; }
-    if (nTe == 0 || nTep == 0) return RTBHIP_OK;
-    const int64_t N = nTe > nTep ? nTe : nTep;
-    if ((nTe != N && nTe != 1) || (nTep != N && nTep != 1)) { set_error("angle_axis: the pose counts must be equal, or one of them 1"); return RTBHIP_EINVAL; }
-    if (!Te || !Tep || !e) { set_error("angle_axis: NULL buffer"); return RTBHIP_EINVAL; }
-    if (mem == RTBHIP_MEM_DEVICE) {
-        if (((uintptr_t)Te | (uintptr_t)Tep | (uintptr_t)e) & 15) { set_error("angle_axis: device buffers must be 16-byte aligned"); return RTBHIP_EINVAL; }
-        DeviceScope dscope;
-        RTB_TRY(dscope.enter_for("angle_axis", e));
-        return launch_angle_axis(Te, nTe, Tep, nTep, N, e, (hipStream_t)stream, method);
-    }
-    Staging st;
-    void *dA, *dB, *dE;
-    RTB_TRY(st.in(Te, (size_t)nTe * 128, &dA));
-    RTB_TRY(st.in(Tep, (size_t)nTep * 128, &dB));
-    RTB_TRY(st.out((size_t)N * 48, &dE));
-    RTB_TRY(launch_angle_axis((const double *)dA, nTe, (const double *)dB, nTep, N, (double *)dE, nullptr, method));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(e, dE, (size_t)N * 48));
-    return RTBHIP_OK;
-}
-
-/* Robot.jacob0_dot / ETS.manipulability (yoshikawa) / ETS.jacobm (SURVEY 8f-4) */
-static int diff_entry(const char *fn, rtbhip_chain_t h, int mode, int axes, const double *q, const double *qd, int64_t N,
-                      const double *tool16, int frame, double *out, int mem, void *stream)
-{
-    const std::shared_ptr<Chain> c_owner = chain_from_handle(h);
-    Chain *c = c_owner.get();
-    RTB_TRACE((std::string("rtbhip_") + fn).c_str());
-    if (!c) { set_error(std::string(fn) + ": unknown chain handle"); return RTBHIP_EINVAL; }
+    const char *fn = "p_servo";
+    RTB_TRACE(fn);
+    if (method != 0 && method != 1) return refuse(fn, "method must be 0 angle-axis or 1 rpy");
     DeviceScope dscope;
-    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
-    if (frame != 0 && frame != 1) { set_error(std::string(fn) + ": frame must be 0 or 1"); return RTBHIP_EINVAL; }
-    if (mode != 0 && mode != 3 && mode != 4 && (axes & 63) == 0) { set_error(std::string(fn) + ": empty axes mask"); return RTBHIP_EINVAL; }
-    if (N > 0 && (!out || ((mode == 0 || mode == 4) && !qd))) { set_error(std::string(fn) + ": NULL qd/output"); return RTBHIP_EINVAL; }
+    int64_t N;
+    RTB_TRY(check_pose_pair(fn, Te, nTe, Tep, nTep, gain6 != nullptr, v, arrived, mem, &dscope, &N));
     if (N == 0) return RTBHIP_OK;
-    DevChain ops;
-    RTB_TRY(chain_device_ops(c, &ops, nullptr));
-    Affine tool = affine_from16(tool16);
-    const size_t n = (size_t)c->n, qw = (size_t)c->q_width;
-    if (mem == RTBHIP_MEM_DEVICE)
-        return launch_kin_diff(c, ops, mode, axes, q, qd, N, tool, frame, out, (hipStream_t)stream);
-    Staging st;
-    void *dq, *dqd = nullptr, *dout;
-    const size_t obytes = (size_t)N * 8 * ((mode == 0 || mode == 3 || mode == 4) ? 6 * n : (mode == 1 ? 1 : n));
-    RTB_TRY(st.in(q, (size_t)N * qw * 8, &dq));
-    if (mode == 0 || mode == 4) RTB_TRY(st.in(qd, (size_t)N * qw * 8, &dqd));
-    RTB_TRY(st.out(obytes, &dout));
-    RTB_TRY(launch_kin_diff(c, ops, mode, axes, (const double *)dq, (const double *)dqd, N, tool, frame, (double *)dout, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(out, dout, obytes));
-    return RTBHIP_OK;
+    Staged st(mem, stream);
+    const double *dA = st.in(Te, (size_t)nTe * 128), *dB = st.in(Tep, (size_t)nTep * 128);
+    double *dV = st.out(v, (size_t)N * 48);
+    unsigned char *dF = st.out(arrived, (size_t)N);
+    RTB_TRY(st.status());
+    return st.finish(launch_p_servo(dA, nTe, dB, nTep, N, method, gain6, threshold, dV, dF, st.stream()));
 }
 
 int rtbhip_jacob_dot(rtbhip_chain_t chain, const double *q, const double *qd, int64_t N, const double *tool16,
@@ -866,60 +1006,54 @@ int rtbhip_jacobm(rtbhip_chain_t chain, const double *q, int64_t N, const double
 int rtbhip_link_frames(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16, const int32_t *marks,
                        int32_t nmarks, double *out, int32_t mem, void *stream)
 {
+    const char *fn = "link_frames";
     const std::shared_ptr<Chain> c_owner = chain_from_handle(chain);
     Chain *c = c_owner.get();
-    RTB_TRACE("rtbhip_link_frames");
-    if (!c) { set_error("link_frames: unknown chain handle"); return RTBHIP_EINVAL; }
-    if (mem != RTBHIP_MEM_HOST && mem != RTBHIP_MEM_DEVICE) { set_error("link_frames: bad mem kind"); return RTBHIP_EINVAL; }
-    if (N < 0) { set_error("link_frames: negative N"); return RTBHIP_EINVAL; }
-    if (nmarks > 0 && !marks) { set_error("link_frames: NULL marks"); return RTBHIP_EINVAL; }
+    RTB_TRACE(fn);
+    if (!c) return refuse(fn, "unknown chain handle");
+    RTB_TRY(check_mem(fn, mem));
+    if (N < 0) return refuse(fn, "negative N");
+    if (nmarks > 0 && !marks) return refuse(fn, "NULL marks");
     FrameTable ft;
     RTB_TRY(compile_frames(c, marks, nmarks, &ft));
     if (N == 0 || nmarks == 0) return RTBHIP_OK;
-    if ((c->q_width > 0 && !q) || !out) { set_error("link_frames: NULL q / output"); return RTBHIP_EINVAL; }
+    if ((c->q_width > 0 && !q) || !out) return refuse(fn, "NULL q / output");
     Affine b = affine_from16(base16);
     ft.has_base = b.used;
     for (int i = 0; i < 12; i++) ft.base[i] = b.v[i];
     DevChain ops;
     RTB_TRY(chain_device_ops(c, &ops, nullptr));
-    if (mem == RTBHIP_MEM_DEVICE) return launch_frames(c, ops, ft, q, N, out, (hipStream_t)stream);
-    Staging st;
-    void *dq, *dout;
-    const size_t obytes = (size_t)N * nmarks * 128;
-    RTB_TRY(st.in(q, (size_t)N * c->q_width * 8, &dq));
-    RTB_TRY(st.out(obytes, &dout));
-    RTB_TRY(launch_frames(c, ops, ft, (const double *)dq, N, (double *)dout, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(out, dout, obytes));
-    return RTBHIP_OK;
+    Staged st(mem, stream);
+    const double *dq = st.in(q, (size_t)N * c->q_width * 8);
+    double *dout = st.out(out, (size_t)N * nmarks * 128);
+    RTB_TRY(st.status());
+    return st.finish(launch_frames(c, ops, ft, dq, N, dout, st.stream()));
 }
 
 /* ETS.partial_fkine0 (robot/ETS.py:1821-2013): order >= 3; orders 1 and 2 are jacob0 / hessian0 */
 int rtbhip_partial_fkine0(rtbhip_chain_t chain, const double *q, int64_t N, const double *tool16, int32_t order,
                           double *out, int32_t mem, void *stream)
 {
+    const char *fn = "partial_fkine0";
     const std::shared_ptr<Chain> c_owner = chain_from_handle(chain);
     Chain *c = c_owner.get();
-    RTB_TRACE("rtbhip_partial_fkine0");
-    if (!c) { set_error("partial_fkine0: unknown chain handle"); return RTBHIP_EINVAL; }
+    RTB_TRACE(fn);
+    if (!c) return refuse(fn, "unknown chain handle");
     DeviceScope dscope;
-    RTB_TRY(check_batch("partial_fkine0", q, N, mem, &dscope));
-    if (order < 3 || order > kPartialMaxOrder) { set_error("partial_fkine0: order must be 3.." + std::to_string(kPartialMaxOrder)); return RTBHIP_EINVAL; }
-    if (c->n < 1) { set_error("partial_fkine0: chain has no joints"); return RTBHIP_EINVAL; }
-    if (N > 0 && !out) { set_error("partial_fkine0: NULL output"); return RTBHIP_EINVAL; }
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    if (order < 3 || order > kPartialMaxOrder) return refuse(fn, ("order must be 3.." + std::to_string(kPartialMaxOrder)).c_str());
+    if (c->n < 1) return refuse(fn, "chain has no joints");
+    if (N > 0 && !out) return refuse(fn, "NULL output");
     if (N == 0) return RTBHIP_OK;
     DevChain ops;
     RTB_TRY(chain_device_ops(c, &ops, nullptr));
     Affine base = affine_from16(nullptr), tool = affine_from16(tool16);
     const int n = c->n;
-    hipStream_t s = mem == RTBHIP_MEM_DEVICE ? (hipStream_t)stream : nullptr;
-    Staging st;
-    void *dq = nullptr, *dout = nullptr;
-    const size_t obytes = (size_t)N * (size_t)partial_size(n, order) * 8;
-    if (mem == RTBHIP_MEM_HOST) {
-        RTB_TRY(st.in(q, (size_t)N * c->q_width * 8, &dq));
-        RTB_TRY(st.out(obytes, &dout));
-    } else { dq = (void *)q; dout = out; }
+    Staged st(mem, stream);
+    const double *dq = st.in(q, (size_t)N * c->q_width * 8);
+    double *dout = st.out(out, (size_t)N * (size_t)partial_size(n, order) * 8);
+    RTB_TRY(st.status());
+    const hipStream_t s = st.stream();
     // the lower-order tensors are stream-ordered temporaries from the device's memory pool (kept cached between
     // calls): the call only enqueues work, as every other device-pointer entry point does
     RTB_TRY(pool_keep_cached());
@@ -934,18 +1068,13 @@ int rtbhip_partial_fkine0(rtbhip_chain_t chain, const double *q, int64_t N, cons
         lower[a - 1] = (double *)p;
     }
     // the two specialised launches (register-resident Jacobian, staged Hessian) beat the combined generic tile
-    if (rc == RTBHIP_OK) rc = launch_kin(c, ops, (const double *)dq, N, base, tool, 0, nullptr, lower[0], nullptr, s);
-    if (rc == RTBHIP_OK && !skip_h) rc = launch_kin(c, ops, (const double *)dq, N, base, tool, 0, nullptr, nullptr, lower[1], s);
+    if (rc == RTBHIP_OK) rc = launch_kin(c, ops, dq, N, base, tool, 0, nullptr, lower[0], nullptr, s);
+    if (rc == RTBHIP_OK && !skip_h) rc = launch_kin(c, ops, dq, N, base, tool, 0, nullptr, nullptr, lower[1], s);
     for (int a = 3; a <= order && rc == RTBHIP_OK; ++a)
-        rc = launch_partial(n, a, lower, N, a == order ? (double *)dout : lower[a - 1], s);
+        rc = launch_partial(n, a, lower, N, a == order ? dout : lower[a - 1], s);
     for (int a = 1; a < order; ++a)
         if (lower[a - 1]) (void)hipFreeAsync(lower[a - 1], s);
-    RTB_TRY(rc);
-    if (mem == RTBHIP_MEM_HOST) {
-        RTB_HIP(hipStreamSynchronize(s));
-        RTB_TRY(fetch(out, dout, obytes));
-    }
-    return RTBHIP_OK;
+    return st.finish(rc);
 }
 
 int rtbhip_ik_lm(rtbhip_chain_t chain, const double *Tep, int64_t N, const double *q0,
@@ -958,15 +1087,6 @@ int rtbhip_ik_lm(rtbhip_chain_t chain, const double *Tep, int64_t N, const doubl
                                   0.0, 0.0, 0.1, nullptr, q_out, success, iters, searches, residual, mem, stream);
 }
 
-static int ik_entry(rtbhip_chain_t chain, const double *Tep, int64_t N, const double *q0,
-                           int32_t ilimit, int32_t slimit, double tol, int32_t reject_jl, const double *we6,
-                           double lambda, int32_t method, int32_t flavour, uint64_t seed,
-                           double kq, double km, double ps, const double *pi, double ks, double *q_out,
-                           int32_t *success, int32_t *iters, int32_t *searches, double *residual,
-                           int32_t mem, void *stream);
-
-// restart-generator key of row 0 for the IK calls this thread makes from now on (rtbhip.h)
-static thread_local int64_t t_ik_target_base = 0;
 int rtbhip_ik_target_base(int64_t base)
 {
     if (base < 0) { set_error("ik_target_base: negative base"); return RTBHIP_EINVAL; }
@@ -995,62 +1115,6 @@ int rtbhip_ik_qp(rtbhip_chain_t chain, const double *Tep, int64_t N, const doubl
                     residual, mem, stream);
 }
 
-static int ik_entry(rtbhip_chain_t chain, const double *Tep, int64_t N, const double *q0,
-                           int32_t ilimit, int32_t slimit, double tol, int32_t reject_jl, const double *we6,
-                           double lambda, int32_t method, int32_t flavour, uint64_t seed,
-                           double kq, double km, double ps, const double *pi, double ks, double *q_out,
-                           int32_t *success, int32_t *iters, int32_t *searches, double *residual,
-                           int32_t mem, void *stream)
-{
-    const std::shared_ptr<Chain> c_owner = chain_from_handle(chain);
-    Chain *c = c_owner.get();
-    RTB_TRACE("rtbhip_ik_lm");
-    if (!c) { set_error("ik_lm: unknown chain handle"); return RTBHIP_EINVAL; }
-    DeviceScope dscope;
-    RTB_TRY(check_batch("ik_lm", Tep, N, mem, &dscope));
-    if (flavour < 0 || flavour > 1) { set_error("ik_lm: flavour must be 0 (ik_LM) or 1 (ikine_LM)"); return RTBHIP_EINVAL; }
-    if (ilimit < 1 || slimit < 1) { set_error("ik_lm: ilimit and slimit must be >= 1"); return RTBHIP_EINVAL; }
-    if (c->n < 1) { set_error("ik_lm: chain has no joints"); return RTBHIP_EINVAL; }
-    if (c->q_width != c->n) { set_error("ik_lm: chain must use jindex 0..n-1 (reference ik.cpp:34-37 assumes the same)"); return RTBHIP_EINVAL; }
-    if (N > 0 && (!q_out || !success || !iters || !searches || !residual)) { set_error("ik_lm: NULL output"); return RTBHIP_EINVAL; }
-    if (N == 0) return RTBHIP_OK;
-    IkParams p;
-    p.ilimit = ilimit; p.slimit = slimit; p.reject_jl = reject_jl ? 1 : 0; p.method = method;
-    p.flavour = flavour; p.tol = tol; p.lambda = lambda; p.seed = seed;
-    p.kq = kq; p.km = km; p.ps = ps; p.ks = ks; p.target0 = t_ik_target_base;
-    for (int j = 0; j < RTBHIP_MAX_JOINTS; ++j) p.pi[j] = pi ? pi[j < c->n ? j : (c->n > 0 ? c->n - 1 : 0)] : 0.3;      // NULL: the reference's default
-    if (kq > 0.0 && flavour != 1) { set_error("ik_lm: null-space terms belong to the Python solvers (flavour 1)"); return RTBHIP_EINVAL; }
-    if (kq > 0.0)
-        for (int j = 0; j < c->n && j < RTBHIP_MAX_JOINTS; ++j)
-            if (ps == p.pi[j]) { set_error("ik_lm: ps must differ from pi"); return RTBHIP_EINVAL; }
-    for (int i = 0; i < 6; i++) p.we[i] = we6 ? we6[i] : 1.0;
-    RTB_TRY(ik_check_limits(c, p, N));                 // what the device build refuses, before the device is touched
-    DevChain ops;
-    const double *qlim = nullptr;
-    RTB_TRY(chain_device_ops(c, &ops, &qlim));
-    const size_t n = (size_t)c->n;
-    if (mem == RTBHIP_MEM_DEVICE)
-        return launch_ik(c, ops, qlim, Tep, N, q0, p, q_out, success, iters, searches, residual, (hipStream_t)stream);
-    Staging st;
-    void *dTep, *dq0, *dq, *ds, *di, *dse, *dr;
-    RTB_TRY(st.in(Tep, (size_t)N * 128, &dTep));
-    RTB_TRY(st.in(q0, (size_t)N * n * 8, &dq0));
-    RTB_TRY(st.out((size_t)N * n * 8, &dq));
-    RTB_TRY(st.out((size_t)N * 4, &ds));
-    RTB_TRY(st.out((size_t)N * 4, &di));
-    RTB_TRY(st.out((size_t)N * 4, &dse));
-    RTB_TRY(st.out((size_t)N * 8, &dr));
-    RTB_TRY(launch_ik(c, ops, qlim, (const double *)dTep, N, (const double *)dq0, p, (double *)dq, (int32_t *)ds,
-                      (int32_t *)di, (int32_t *)dse, (double *)dr, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(q_out, dq, (size_t)N * n * 8));
-    RTB_TRY(fetch(success, ds, (size_t)N * 4));
-    RTB_TRY(fetch(iters, di, (size_t)N * 4));
-    RTB_TRY(fetch(searches, dse, (size_t)N * 4));
-    RTB_TRY(fetch(residual, dr, (size_t)N * 8));
-    return RTBHIP_OK;
-}
-
 int rtbhip_ik_restart(rtbhip_chain_t chain, uint64_t seed, int64_t target, int32_t search, double *q_n)
 {
     const std::shared_ptr<Chain> c_owner = chain_from_handle(chain);
@@ -1060,7 +1124,6 @@ int rtbhip_ik_restart(rtbhip_chain_t chain, uint64_t seed, int64_t target, int32
     return RTBHIP_OK;
 }
 
-static int g_rne_pszero = 1;      // rtbhip_tune("rne_pszero", 0): handles created afterwards do not take the p* = 0 shortcut (A/B; same values)
 int rtbhip_dyn_create(const double *L24, int32_t n, int32_t mdh, rtbhip_dyn_t *dyn)
 {
     if (!L24 || !dyn || n < 1) { set_error("dyn_create: bad argument"); return RTBHIP_EINVAL; }
@@ -1087,86 +1150,27 @@ int rtbhip_dyn_create(const double *L24, int32_t n, int32_t mdh, rtbhip_dyn_t *d
         if (k.I[1] == 0.0 && k.I[2] == 0.0 && k.I[3] == 0.0 && k.I[5] == 0.0 && k.I[6] == 0.0 && k.I[7] == 0.0) k.flags |= kLinkIDiag;
         if (g_rne_pszero && k.sigma == 0 && k.a == 0.0 && k.d == 0.0) k.flags |= kLinkPsZero;      // p* = 0 (DH Panda links 2 and 6, Puma560 link 5 and 6)
     }
-    uint64_t h = g_next.fetch_add(1);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    // a table without a built-in instantiation: ask for its own now (worker thread; nobody waits), the first launches take the general kernels
-    jit_request_dyn(d.get(), false, false);
-    g_dyns[h] = std::move(d);
-    *dyn = h;
+    jit_request_dyn(d.get(), false, false);       // a table without a built-in instantiation: its own
+    *dyn = g_dyns.add(std::move(d));
     return RTBHIP_OK;
-}
-
-int rtbhip_dyn_destroy(rtbhip_dyn_t dyn)
-{
-    std::shared_ptr<Dyn> d;
-    {
-        std::lock_guard<std::mutex> lk(g_reg_mu);
-        auto it = g_dyns.find(dyn);
-        if (it == g_dyns.end()) { set_error("dyn_destroy: unknown handle"); return RTBHIP_EINVAL; }
-        d = std::move(it->second);
-        g_dyns.erase(it);
-    }
-    return RTBHIP_OK;
-}
-
-static int rne_entry(const char *fn, rtbhip_dyn_t dyn, const double *q, const double *qd, const double *qdd, int64_t N,
-                     const double *grav3, const double *fext6, double *tau, double *wbase, bool want_wbase, int32_t mem, void *stream)
-{
-    const std::shared_ptr<Dyn> d_owner = dyn_from_handle(dyn);
-    Dyn *d = d_owner.get();
-    if (!d) { set_error(std::string(fn) + ": unknown dyn handle"); return RTBHIP_EINVAL; }
-    DeviceScope dscope;
-    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
-    if (!grav3) { set_error(std::string(fn) + ": NULL gravity"); return RTBHIP_EINVAL; }
-    if (N > 0 && !tau) { set_error(std::string(fn) + ": NULL tau"); return RTBHIP_EINVAL; }   // qd / qdd may be NULL (= zeros)
-    if (want_wbase && N > 0 && !wbase) { set_error(std::string(fn) + ": NULL wbase"); return RTBHIP_EINVAL; }
-    if (N == 0) return RTBHIP_OK;
-    const DevLink *links = nullptr;
-    RTB_TRY(dyn_device_links(d, &links));
-    if (mem == RTBHIP_MEM_DEVICE)
-        return launch_rne(d, links, q, qd, qdd, N, grav3, fext6, tau, (hipStream_t)stream, wbase);
-    HostIO io;
-    const size_t row = (size_t)d->n * 8;
-    io.add_in(q, row); io.add_in(qd, row); io.add_in(qdd, row);
-    io.add_out(tau, row);
-    if (want_wbase) io.add_out(wbase, 6 * 8);
-    return host_pipeline(io, N, [&](const void *const *din, void *const *dout, int64_t, int64_t rows, hipStream_t s) {
-        return launch_rne(d, links, (const double *)din[0], (const double *)din[1], (const double *)din[2], rows, grav3, fext6, (double *)dout[0], s,
-                          want_wbase ? (double *)dout[1] : nullptr);
-    });
 }
 
 int rtbhip_rne(rtbhip_dyn_t dyn, const double *q, const double *qd, const double *qdd, int64_t N,
                const double *grav3, const double *fext6, double *tau, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_rne");
-    return rne_entry("rne", dyn, q, qd, qdd, N, grav3, fext6, tau, nullptr, false, mem, stream);
+    return rne_entry<double>("rne", dyn, q, qd, qdd, N, grav3, fext6, tau, nullptr, false, mem, stream);
 }
 
 int rtbhip_rne_f32(rtbhip_dyn_t dyn, const float *q, const float *qd, const float *qdd, int64_t N,
                    const double *grav3, const double *fext6, float *tau, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_rne_f32");
-    const char *fn = "rne_f32";
-    const std::shared_ptr<Dyn> d_owner = dyn_from_handle(dyn);
-    Dyn *d = d_owner.get();
-    if (!d) { set_error(std::string(fn) + ": unknown dyn handle"); return RTBHIP_EINVAL; }
-    DeviceScope dscope;
-    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
-    RTB_TRY(check_f32_device(fn, mem));
-    if (!grav3) { set_error(std::string(fn) + ": NULL gravity"); return RTBHIP_EINVAL; }
-    if (N > 0 && !tau) { set_error(std::string(fn) + ": NULL tau"); return RTBHIP_EINVAL; }   // qd / qdd may be NULL (= zeros)
-    if (N == 0) return RTBHIP_OK;
-    const DevLink *links = nullptr;
-    RTB_TRY(dyn_device_links(d, &links));
-    return launch_rne_f32(d, links, q, qd, qdd, N, grav3, fext6, tau, (hipStream_t)stream);
+    return rne_entry<float>("rne_f32", dyn, q, qd, qdd, N, grav3, fext6, tau, nullptr, false, mem, stream);
 }
 
 int rtbhip_rne_base_wrench(rtbhip_dyn_t dyn, const double *q, const double *qd, const double *qdd, int64_t N,
                            const double *grav3, const double *fext6, double *tau, double *wbase, int32_t mem, void *stream)
 {
-    RTB_TRACE("rtbhip_rne_base_wrench");
-    return rne_entry("rne_base_wrench", dyn, q, qd, qdd, N, grav3, fext6, tau, wbase, true, mem, stream);
+    return rne_entry<double>("rne_base_wrench", dyn, q, qd, qdd, N, grav3, fext6, tau, wbase, true, mem, stream);
 }
 
 int rtbhip_tree_create(const rtbhip_tree_group *groups, int32_t ng, rtbhip_tree_t *tree)
@@ -1175,86 +1179,31 @@ int rtbhip_tree_create(const rtbhip_tree_group *groups, int32_t ng, rtbhip_tree_
     std::shared_ptr<Tree> t(new Tree());
     RTB_TRY(compile_tree(groups, ng, t.get()));
     jit_request_tree(t.get(), false, false);
-    const uint64_t h = g_next.fetch_add(1);
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_trees[h] = std::move(t);
-    *tree = h;
-    return RTBHIP_OK;
-}
-
-int rtbhip_tree_destroy(rtbhip_tree_t tree)
-{
-    std::shared_ptr<Tree> t;
-    {
-        std::lock_guard<std::mutex> lk(g_reg_mu);
-        auto it = g_trees.find(tree);
-        if (it == g_trees.end()) { set_error("tree_destroy: unknown handle"); return RTBHIP_EINVAL; }
-        t = std::move(it->second);
-        g_trees.erase(it);
-    }
+    *tree = g_trees.add(std::move(t));
     return RTBHIP_OK;
 }
 
 int rtbhip_tree_rne(rtbhip_tree_t tree, const double *q, const double *qd, const double *qdd, int64_t N,
                     const double *gravity3, double *tau, int32_t mem, void *stream)
 {
+    const char *fn = "tree_rne";
     const std::shared_ptr<Tree> t_owner = tree_from_handle(tree);
     Tree *t = t_owner.get();
-    RTB_TRACE("rtbhip_tree_rne");
-    if (!t) { set_error("tree_rne: unknown tree handle"); return RTBHIP_EINVAL; }
+    RTB_TRACE(fn);
+    if (!t) return refuse(fn, "unknown tree handle");
     DeviceScope dscope;
-    RTB_TRY(check_batch("tree_rne", q, N, mem, &dscope));
-    if (!gravity3) { set_error("tree_rne: NULL gravity"); return RTBHIP_EINVAL; }
-    if (N > 0 && !tau) { set_error("tree_rne: NULL tau"); return RTBHIP_EINVAL; }
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    if (!gravity3) return refuse(fn, "NULL gravity");
+    if (N > 0 && !tau) return refuse(fn, "NULL tau");
     if (N == 0) return RTBHIP_OK;
     const DevGroup *groups = nullptr;
     RTB_TRY(tree_device_groups(t, &groups));
-    if (mem == RTBHIP_MEM_DEVICE)
-        return launch_tree_rne(t, groups, q, qd, qdd, N, gravity3, tau, (hipStream_t)stream);
-    Staging st;
+    Staged st(mem, stream);
     const size_t bytes = (size_t)N * t->n * 8;
-    void *dq, *dqd, *dqdd, *dtau;
-    RTB_TRY(st.in(q, bytes, &dq));
-    RTB_TRY(st.in(qd, bytes, &dqd));
-    RTB_TRY(st.in(qdd, bytes, &dqdd));
-    RTB_TRY(st.out(bytes, &dtau));
-    RTB_TRY(launch_tree_rne(t, groups, (const double *)dq, (const double *)dqd, (const double *)dqdd, N, gravity3,
-                            (double *)dtau, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(tau, dtau, bytes));
-    return RTBHIP_OK;
-}
-
-/* Dynamics.inertia / coriolis / accel (robot/Dynamics.py:704-861, 424-509) */
-static int dyn_entry(const char *fn, rtbhip_dyn_t dyn, int mode, const double *q, const double *qd, const double *tq,
-                     int64_t N, const double *grav3, double *out, int32_t mem, void *stream)
-{
-    const std::shared_ptr<Dyn> d_owner = dyn_from_handle(dyn);
-    Dyn *d = d_owner.get();
-    RTB_TRACE((std::string("rtbhip_") + fn).c_str());
-    if (!d) { set_error(std::string(fn) + ": unknown dyn handle"); return RTBHIP_EINVAL; }
-    DeviceScope dscope;
-    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
-    if (N > 0 && !out) { set_error(std::string(fn) + ": NULL output"); return RTBHIP_EINVAL; }
-    if (N > 0 && mode >= 1 && !qd) { set_error(std::string(fn) + ": NULL qd"); return RTBHIP_EINVAL; }
-    if (N > 0 && mode == 2 && (!tq || !grav3)) { set_error(std::string(fn) + ": NULL torque/gravity"); return RTBHIP_EINVAL; }
-    if (N == 0) return RTBHIP_OK;
-    const DevLink *links = nullptr;
-    RTB_TRY(dyn_device_links(d, &links));
-    if (mem == RTBHIP_MEM_DEVICE)
-        return launch_dyn(d, links, mode, q, qd, tq, N, grav3, out, (hipStream_t)stream);
-    Staging st;
-    const size_t n = (size_t)d->n, bytes = (size_t)N * n * 8, obytes = mode == 2 ? bytes : bytes * n;
-    void *dq, *dqd = nullptr, *dtq = nullptr, *dout;
-    RTB_TRY(st.in(q, bytes, &dq));
-    if (mode >= 1) RTB_TRY(st.in(qd, bytes, &dqd));
-    if (mode == 2) RTB_TRY(st.in(tq, bytes, &dtq));
-    RTB_TRY(st.out(obytes, &dout));
-    RTB_TRY(launch_dyn(d, links, mode, (const double *)dq, (const double *)dqd, (const double *)dtq, N, grav3,
-                       (double *)dout, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(out, dout, obytes));
-    return RTBHIP_OK;
+    const double *dq = st.in(q, bytes), *dqd = st.in(qd, bytes), *dqdd = st.in(qdd, bytes);
+    double *dtau = st.out(tau, bytes);
+    RTB_TRY(st.status());
+    return st.finish(launch_tree_rne(t, groups, dq, dqd, dqdd, N, gravity3, dtau, st.stream()));
 }
 
 int rtbhip_inertia(rtbhip_dyn_t dyn, const double *q, int64_t N, double *M, int32_t mem, void *stream)
@@ -1273,38 +1222,6 @@ int rtbhip_accel(rtbhip_dyn_t dyn, const double *q, const double *qd, const doub
     return dyn_entry("accel", dyn, 2, q, qd, torque, N, grav3, qdd, mem, stream);
 }
 
-/* the same terms for an ETS robot (link tree): Dynamics.inertia / coriolis / accel over Robot.rne */
-static int tree_dyn_entry(const char *fn, rtbhip_tree_t tree, int mode, const double *q, const double *qd, const double *tq,
-                          int64_t N, const double *grav3, double *out, int32_t mem, void *stream)
-{
-    const std::shared_ptr<Tree> t_owner = tree_from_handle(tree);
-    Tree *t = t_owner.get();
-    RTB_TRACE((std::string("rtbhip_") + fn).c_str());
-    if (!t) { set_error(std::string(fn) + ": unknown tree handle"); return RTBHIP_EINVAL; }
-    DeviceScope dscope;
-    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
-    if (N > 0 && !out) { set_error(std::string(fn) + ": NULL output"); return RTBHIP_EINVAL; }
-    if (N > 0 && mode >= 1 && !qd) { set_error(std::string(fn) + ": NULL qd"); return RTBHIP_EINVAL; }
-    if (N > 0 && mode == 2 && (!tq || !grav3)) { set_error(std::string(fn) + ": NULL torque/gravity"); return RTBHIP_EINVAL; }
-    if (N == 0) return RTBHIP_OK;
-    const DevGroup *groups = nullptr;
-    RTB_TRY(tree_device_groups(t, &groups));
-    if (mem == RTBHIP_MEM_DEVICE)
-        return launch_tree_dyn(t, groups, mode, q, qd, tq, N, grav3, out, (hipStream_t)stream);
-    Staging st;
-    const size_t n = (size_t)t->n, bytes = (size_t)N * n * 8, obytes = mode == 2 ? bytes : bytes * n;
-    void *dq, *dqd = nullptr, *dtq = nullptr, *dout;
-    RTB_TRY(st.in(q, bytes, &dq));
-    if (mode >= 1) RTB_TRY(st.in(qd, bytes, &dqd));
-    if (mode == 2) RTB_TRY(st.in(tq, bytes, &dtq));
-    RTB_TRY(st.out(obytes, &dout));
-    RTB_TRY(launch_tree_dyn(t, groups, mode, (const double *)dq, (const double *)dqd, (const double *)dtq, N, grav3,
-                            (double *)dout, nullptr));
-    RTB_HIP(hipDeviceSynchronize());
-    RTB_TRY(fetch(out, dout, obytes));
-    return RTBHIP_OK;
-}
-
 int rtbhip_tree_inertia(rtbhip_tree_t tree, const double *q, int64_t N, double *M, int32_t mem, void *stream)
 {
     return tree_dyn_entry("tree_inertia", tree, 0, q, nullptr, nullptr, N, nullptr, M, mem, stream);
@@ -1319,61 +1236,6 @@ int rtbhip_tree_accel(rtbhip_tree_t tree, const double *q, const double *qd, con
                       const double *gravity3, double *qdd, int32_t mem, void *stream)
 {
     return tree_dyn_entry("tree_accel", tree, 2, q, qd, torque, N, gravity3, qdd, mem, stream);
-}
-
-static int fleet_entry(const rtbhip_chain_t *chains, int32_t n_chains, const double *const *q,
-                       const int64_t *N, int32_t frame, double *const *T, double *const *J,
-                       int32_t mem, void *stream, bool packed)
-{
-    // packed: T[c] is the (N[c], 16 + 6 n_c) array of [T | J] rows, J is not used
-    if (n_chains < 0 || (n_chains > 0 && (!chains || !q || !N || !T || (!packed && !J)))) { set_error("fleet: bad argument"); return RTBHIP_EINVAL; }
-    RTB_TRACE(packed ? "rtbhip_fleet_fkine_jacob_packed" : "rtbhip_fleet_fkine_jacob");
-    if (frame != 0 && frame != 1) { set_error("fleet: frame must be 0 or 1"); return RTBHIP_EINVAL; }
-    if (mem != RTBHIP_MEM_HOST && mem != RTBHIP_MEM_DEVICE) { set_error("fleet: bad mem kind"); return RTBHIP_EINVAL; }
-    std::vector<FleetEntry> entries;
-    Staging st;
-    DeviceScope dscope;
-    if (mem == RTBHIP_MEM_DEVICE)
-        for (int i = 0; i < n_chains; i++)
-            if (N[i] > 0 && q[i]) { RTB_TRY(dscope.enter_for("fleet", q[i])); break; }
-    std::vector<void *> dT(n_chains, nullptr), dJ(n_chains, nullptr);
-    int64_t tile0 = 0;
-    for (int i = 0; i < n_chains; i++) {
-        const std::shared_ptr<Chain> c_owner = chain_from_handle(chains[i]);
-        Chain *c = c_owner.get();
-        if (!c) { set_error("fleet: unknown chain handle"); return RTBHIP_EINVAL; }
-        if (N[i] < 0) { set_error("fleet: negative N"); return RTBHIP_EINVAL; }
-        if (N[i] == 0) continue;
-        if (!q[i] || !T[i] || (!packed && !J[i])) { set_error("fleet: NULL buffer"); return RTBHIP_EINVAL; }
-        FleetEntry e;
-        RTB_TRY(chain_device_ops(c, &e.dc, nullptr));
-        e.n = c->n; e.q_width = c->q_width; e.N = N[i]; e.tile0 = tile0;
-        e.stride = 0; e.pad = 0;
-        if (mem == RTBHIP_MEM_DEVICE) {
-            e.q = q[i]; e.T = T[i]; e.J = packed ? nullptr : J[i];
-        } else {
-            void *dq;
-            RTB_TRY(st.in(q[i], (size_t)N[i] * c->q_width * 8, &dq));
-            RTB_TRY(st.out((size_t)N[i] * (packed ? 128 + 48 * c->n : 128), &dT[i]));
-            if (!packed) RTB_TRY(st.out((size_t)N[i] * 48 * c->n, &dJ[i]));
-            e.q = (const double *)dq; e.T = (double *)dT[i]; e.J = (double *)dJ[i];
-        }
-        tile0 += (N[i] + 63) / 64;
-        entries.push_back(e);
-    }
-    if (entries.empty()) return RTBHIP_OK;
-    RTB_TRY(launch_fleet(entries, frame, mem == RTBHIP_MEM_DEVICE ? (hipStream_t)stream : nullptr, packed));
-    if (mem == RTBHIP_MEM_HOST) {
-        RTB_HIP(hipDeviceSynchronize());
-        for (int i = 0; i < n_chains; i++) {
-            if (N[i] == 0) continue;
-            const std::shared_ptr<Chain> c_owner = chain_from_handle(chains[i]);
-            Chain *c = c_owner.get();
-            RTB_TRY(fetch(T[i], dT[i], (size_t)N[i] * (packed ? 128 + 48 * c->n : 128)));
-            if (!packed) RTB_TRY(fetch(J[i], dJ[i], (size_t)N[i] * 48 * c->n));
-        }
-    }
-    return RTBHIP_OK;
 }
 
 int rtbhip_fleet_fkine_jacob(const rtbhip_chain_t *chains, int32_t n_chains, const double *const *q,
