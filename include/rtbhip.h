@@ -150,6 +150,26 @@ int rtbhip_hessian(rtbhip_chain_t chain, const double *q, int64_t N, const doubl
  * 16-byte aligned. */
 int rtbhip_hessian_from_jacobian(const double *J, int64_t N, int32_t n, double *H, int32_t mem, void *stream);
 
+/* VECTOR-JACOBIAN PRODUCT of rtbhip_fkine_jacob (frame 0) -- the backward pass of a loss on T and / or J; no reference counterpart.  What is
+ * differentiated: T = base * _ETS_fkine(q) * tool (core/methods.cpp:318-352), whose derivative with respect to q_k is the Jacobian column acting
+ * on the pose (_ETS_jacob0, methods.cpp:112-207), and J = _ETS_jacob0(q, tool), whose derivative is _ETS_hessian (methods.cpp:16-32).
+ * gT (N,16) is the loss's gradient with respect to T (row-major 4x4, the bottom row is not looked at), gJ (N,6,n) with respect to J; either may
+ * be NULL (a loss on the other alone), not both.  gq (N, q_width): gq[i,c] = sum gT[i] dT[i]/dq_c + sum gJ[i] dJ[i]/dq_c; a column no joint of
+ * the chain reads is written as zero.  base16 / tool16: those of the forward call (base16 acts on T only, as there).  One fused kernel for
+ * chains of 1..10 joints (T, J and the Hessian are never formed in memory); longer chains run the forward launch into temporaries and then the
+ * kernel of rtbhip_kin_vjp_from_jacobian.  RTBHIP_EINVAL for a chain without joints. */
+int rtbhip_fkine_jacob_vjp(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16, const double *tool16,
+                           const double *gT, const double *gJ, double *gq, int32_t mem, void *stream);
+/* ... with q, gT, gJ and gq held as float in device memory (see rtbhip_fkine_jacob_f32: values are widened after their load, the arithmetic
+ * is fp64, gq is rounded once; mem must be RTBHIP_MEM_DEVICE; 4-byte alignment is enough). */
+int rtbhip_fkine_jacob_vjp_f32(rtbhip_chain_t chain, const float *q, int64_t N, const double *base16, const double *tool16,
+                               const float *gT, const float *gJ, float *gq, int32_t mem, void *stream);
+/* The same contraction from a SUPPLIED pose T (N,16; not looked at when gT is NULL) and Jacobian J (N,6,n) in the start frame, n = 1..32: a pure
+ * function of the arrays (as rtbhip_hessian_from_jacobian is of J: the derivative of column c of _ETS_jacob0 with respect to q_k is a cross
+ * product of columns k and c, methods.cpp:16-32), so no chain handle.  gq is (N,n). */
+int rtbhip_kin_vjp_from_jacobian(const double *T, const double *J, const double *gT, const double *gJ, int64_t N, int32_t n, double *gq,
+                                 int32_t mem, void *stream);
+
 /* Robot.manipulability(J=...) (robot/Robot.py:701-905: `if J is not None: w = [mfunc(self, J, q, axes_list)]` :896) and
  * Robot.jacobm(J=..., H=...) (robot/Robot.py:1101-1235: `verifymatrix(J, (6, n))` :1201, `H = self.hessian0(J0=J)` :1206), batched:
  * pure functions of the supplied arrays, so no chain handle.  J is (N,6,n), n = 1..16; m is (N); Jm is (N,n); H is (N,n,6,n) or NULL

@@ -430,6 +430,44 @@ int kin_entry(const char *fn, rtbhip_chain_t h, const R *q, int64_t N, const dou
     return kin_run(c, ops, q, N, affine_from16(base16), affine_from16(tool16), frame, T, J, H, TJ, mem, stream);
 }
 
+}  // namespace
+// the launchers of the vector-Jacobian products (kin_kernels.hip); declared here, not in rtbhip_internal.h: that header is part of the text
+// handed to the run-time compiler, whose code-object keys these host-only declarations have no business changing
+int launch_kin_vjp(const Chain *c, const DevChain &dc, const double *q, int64_t N, const Affine &base, const Affine &tool, const double *gT,
+                   const double *gJ, double *gq, hipStream_t s);
+int launch_kin_vjp_f32(const Chain *c, const DevChain &dc, const float *q, int64_t N, const Affine &base, const Affine &tool, const float *gT,
+                       const float *gJ, float *gq, hipStream_t s);
+int launch_vjp_from_jac(int n, const double *T, const double *J, const double *gT, const double *gJ, int64_t N, double *gq, hipStream_t s);
+namespace {
+
+// rtbhip_fkine_jacob_vjp / rtbhip_fkine_jacob_vjp_f32: the gradient of a loss on fkine and / or jacob0 with respect to q (kin_kernels.hip: k_kin_vjp)
+template <class R>
+int kin_vjp_entry(const char *fn, rtbhip_chain_t h, const R *q, int64_t N, const double *base16, const double *tool16, const R *gT, const R *gJ,
+                  R *gq, int mem, void *stream)
+{
+    const std::shared_ptr<Chain> c_owner = chain_from_handle(h);
+    Chain *c = c_owner.get();
+    RTB_TRACE(fn);
+    if (!c) return refuse(fn, "unknown chain handle");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    RTB_TRY(check_row_type<R>(fn, mem));
+    if (N > 0 && !gq) return refuse(fn, "NULL gq");
+    if (N > 0 && !gT && !gJ) return refuse(fn, "gT and gJ are both NULL: there is nothing to differentiate");
+    if (c->n < 1) return refuse(fn, "chain has no joints");
+    if (N == 0) return RTBHIP_OK;
+    DevChain ops;
+    RTB_TRY(chain_device_ops(c, &ops, nullptr));
+    const size_t rows = (size_t)N, n = (size_t)c->n, qbytes = rows * c->q_width * sizeof(R);
+    Staged st(mem, stream);
+    const R *dq = st.in(q, qbytes), *dgT = st.in(gT, rows * 16 * sizeof(R)), *dgJ = st.in(gJ, rows * 6 * n * sizeof(R));
+    R *dgq = st.out(gq, qbytes);
+    RTB_TRY(st.status());
+    const Affine base = affine_from16(base16), tool = affine_from16(tool16);
+    if constexpr (std::is_same<R, float>::value) return st.finish(launch_kin_vjp_f32(c, ops, dq, N, base, tool, dgT, dgJ, dgq, st.stream()));
+    else return st.finish(launch_kin_vjp(c, ops, dq, N, base, tool, dgT, dgJ, dgq, st.stream()));
+}
+
 /* Robot.manipulability(J=...) / Robot.jacobm(J=..., H=...) (robot/Robot.py:701-905, :1101-1235): pure functions of the supplied arrays */
 int diff_from_jac_entry(const char *fn, int mode, const double *J, const double *H, int64_t N, int32_t n, int32_t axes, double *out,
                         int32_t mem, void *stream)
@@ -921,6 +959,40 @@ int rtbhip_hessian_from_jacobian(const double *J, int64_t N, int32_t n, double *
     double *dH = st.out(H, jb * n);
     RTB_TRY(st.status());
     return st.finish(launch_hess_from_jac(n, dJ, N, dH, st.stream()));
+}
+
+/* the gradient of a loss on T = base * _ETS_fkine(q) * tool (core/methods.cpp:318-352) and J = _ETS_jacob0(q, tool) (:112-207) with respect to q */
+int rtbhip_fkine_jacob_vjp(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16, const double *tool16, const double *gT,
+                           const double *gJ, double *gq, int32_t mem, void *stream)
+{
+    return kin_vjp_entry<double>("fkine_jacob_vjp", chain, q, N, base16, tool16, gT, gJ, gq, mem, stream);
+}
+
+int rtbhip_fkine_jacob_vjp_f32(rtbhip_chain_t chain, const float *q, int64_t N, const double *base16, const double *tool16, const float *gT,
+                               const float *gJ, float *gq, int32_t mem, void *stream)
+{
+    return kin_vjp_entry<float>("fkine_jacob_vjp_f32", chain, q, N, base16, tool16, gT, gJ, gq, mem, stream);
+}
+
+/* ... from a supplied pose and Jacobian: d(column c of _ETS_jacob0)/dq_k is a cross product of columns k and c (_ETS_hessian, core/methods.cpp:16-32) */
+int rtbhip_kin_vjp_from_jacobian(const double *T, const double *J, const double *gT, const double *gJ, int64_t N, int32_t n, double *gq,
+                                 int32_t mem, void *stream)
+{
+    const char *fn = "kin_vjp_from_jacobian";
+    RTB_TRACE(fn);
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, J, N, mem, &dscope));
+    if (n < 1 || n > RTBHIP_MAX_JOINTS) return refuse(fn, "n must be 1..RTBHIP_MAX_JOINTS", RTBHIP_ELIMIT);
+    if (N > 0 && !gq) return refuse(fn, "NULL gq");
+    if (N > 0 && !gT && !gJ) return refuse(fn, "gT and gJ are both NULL: there is nothing to differentiate");
+    if (N > 0 && gT && !T) return refuse(fn, "gT needs T");
+    if (N == 0) return RTBHIP_OK;
+    Staged st(mem, stream);
+    const size_t rows = (size_t)N, jb = rows * 48 * n;
+    const double *dT = st.in(gT ? T : nullptr, rows * 128), *dJ = st.in(J, jb), *dgT = st.in(gT, rows * 128), *dgJ = st.in(gJ, jb);
+    double *dgq = st.out(gq, rows * 8 * n);
+    RTB_TRY(st.status());
+    return st.finish(launch_vjp_from_jac(n, dT, dJ, dgT, dgJ, N, dgq, st.stream()));
 }
 
 int rtbhip_manipulability_from_jacobian(const double *J, int64_t N, int32_t n, int32_t axes_mask, int32_t method, double *m, int32_t mem, void *stream)

@@ -908,4 +908,349 @@ static int launch_fleet_class(int cls, const std::vector<FleetEntry> &entries, i
     return RTBHIP_OK;
 }
 
+// ---------------------------------------------------------------- vector-Jacobian products of fkine / jacob0 (the backward pass of rtbhip/autograd.py)
+// Given the gradients gT (N,4,4; bottom row ignored) and gJ (N,6,n) of a scalar loss with respect to T = base * P(q) and J = jacob0(q), the kernels
+// below return gq (N, q_width), gq[k] = sum gT dT/dq_k + sum gJ dJ/dq_k.  No reference counterpart: the reference has no derivative of a loss; what
+// is differentiated is _ETS_fkine (core/methods.cpp:318-352) and _ETS_jacob0 (:112-207), whose derivative with respect to q is _ETS_hessian (:16-32).
+//   fkine   dP/dq_k is the Jacobian column acting on P: dR/dq_k = [w_k]x R, dp/dq_k = v_k, so the pose term is
+//               gq_k = v_k . g_p + w_k . m,     g_p = translation column of B^T gT,   m = sum_c R_c x (B^T gT)_c     (one 6-vector per row)
+//   jacob0  dJ[:,c]/dq_k = (w_k x v_c ; w_k x w_c) for k <= c and (w_c x v_k ; 0) for k > c (methods.cpp:16-32), so with a . (b x c) = b . (c x a)
+//               gq_k = w_k . S_k + v_k . A_k,   S_k = sum_{c >= k} (v_c x gv_c + w_c x gw_c),   A_k = sum_{c < k} gv_c x w_c
+//           one suffix and one prefix running sum over the columns: O(n), the (n,6,n) Hessian is never formed.
+// Prismatic joints (w = 0, v = z) and flipped joints (the walk negated the column) need nothing extra: the finished columns carry both.
+// Every sum of two products is written out (kin_device.h: mix_pp and friends).
+template <class G>
+RTB_HD void vjp_pose_pullback(const Pose &P, int has_base, const double *base /* row-major 3x4 */, G g /* g(4 r + c): row r, column c of gT */, double (&w)[6])
+{
+#pragma clang fp contract(off)
+    double h[12];      // B_R^T gT (top three rows)
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            h[4 * i + c] = has_base ? dot3x(base[i], g(c), base[4 + i], g(4 + c), base[8 + i], g(8 + c)) : g(4 * i + c);
+    w[0] = h[3]; w[1] = h[7]; w[2] = h[11];
+    w[3] = (mix_pm(P.r10, h[8], P.r20, h[4]) + mix_pm(P.r11, h[9], P.r21, h[5])) + mix_pm(P.r12, h[10], P.r22, h[6]);
+    w[4] = (mix_pm(P.r20, h[0], P.r00, h[8]) + mix_pm(P.r21, h[1], P.r01, h[9])) + mix_pm(P.r22, h[2], P.r02, h[10]);
+    w[5] = (mix_pm(P.r00, h[4], P.r10, h[0]) + mix_pm(P.r01, h[5], P.r11, h[1])) + mix_pm(P.r02, h[6], P.r12, h[2]);
+}
+
+// The contraction.  J(r n + c) / G(r n + c): entry (r, c) of the row's finished Jacobian / of gJ; w = (g_p ; m) of the pose term (zeros without gT);
+// acc(k, x): gq_k += x (the receiver starts at zero; two joints may share a q column).  n is a compile-time constant in the register tile (the
+// loops unroll, every index is static) and a run-time value in k_vjp_from_jac_any.
+template <bool WANT_GJ, class JGet, class GGet, class Acc>
+RTB_HD void vjp_contract(int n, const double (&w)[6], JGet J, GGet G, Acc acc)
+{
+#pragma clang fp contract(off)
+    if (!WANT_GJ) {
+#pragma unroll
+        for (int k = 0; k < n; ++k)
+            acc(k, dot3x(J(k), w[0], J(n + k), w[1], J(2 * n + k), w[2]) + dot3x(J(3 * n + k), w[3], J(4 * n + k), w[4], J(5 * n + k), w[5]));
+        return;
+    }
+    double sx = w[3], sy = w[4], sz = w[5];      // m + S_k
+#pragma unroll
+    for (int k = n - 1; k >= 0; --k) {
+        const double vx = J(k), vy = J(n + k), vz = J(2 * n + k), ox = J(3 * n + k), oy = J(4 * n + k), oz = J(5 * n + k);
+        const double gvx = G(k), gvy = G(n + k), gvz = G(2 * n + k), gwx = G(3 * n + k), gwy = G(4 * n + k), gwz = G(5 * n + k);
+        sx = sx + (mix_pm(vy, gvz, vz, gvy) + mix_pm(oy, gwz, oz, gwy));
+        sy = sy + (mix_pm(vz, gvx, vx, gvz) + mix_pm(oz, gwx, ox, gwz));
+        sz = sz + (mix_pm(vx, gvy, vy, gvx) + mix_pm(ox, gwy, oy, gwx));
+        acc(k, dot3x(ox, sx, oy, sy, oz, sz));
+    }
+    double ax = w[0], ay = w[1], az = w[2];      // g_p + A_k
+#pragma unroll
+    for (int k = 0; k < n; ++k) {
+        const double ox = J(3 * n + k), oy = J(4 * n + k), oz = J(5 * n + k);
+        const double gvx = G(k), gvy = G(n + k), gvz = G(2 * n + k);
+        acc(k, dot3x(J(k), ax, J(n + k), ay, J(2 * n + k), az));
+        ax = ax + mix_pm(gvy, oz, gvz, oy);
+        ay = ay + mix_pm(gvz, ox, gvx, oz);
+        az = az + mix_pm(gvx, oy, gvy, ox);
+    }
+}
+
+// kin_flush in reverse: `cnt` consecutive rows of W values (W even, contiguous in global memory) into LDS rows of `stride` doubles, widened after
+// the load.  Lane l reads the pairs l, l + 64, ... of the run.  A pointer is only assumed aligned to its element (views of tensors are legal).
+template <class S>
+RTB_HD void vjp_fill(const S *__restrict__ src, int W, int cnt, double *rows, int stride, int lane)
+{
+    const int total = cnt * W;
+    int f = 2 * lane;
+    int r = f / W, e = f - r * W;
+    const int da = 128 / W, db = 128 - da * W;
+    for (; f < total; f += 128) {
+        double a, b;
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (sizeof(S) == 4) {
+            typedef float v2f __attribute__((ext_vector_type(2)));
+            typedef v2f v2f_a4 __attribute__((aligned(4)));
+            const v2f v = *reinterpret_cast<const v2f_a4 *>(src + f);
+            a = v.x; b = v.y;
+        } else {
+            typedef double v2d __attribute__((ext_vector_type(2)));
+            typedef v2d v2d_a8 __attribute__((aligned(8)));
+            const v2d v = *reinterpret_cast<const v2d_a8 *>(src + f);
+            a = v.x; b = v.y;
+        }
+#else
+        a = src[f]; b = src[f + 1];
+#endif
+        double *dst = rows + r * stride + e;
+        dst[0] = a; dst[1] = b;
+        e += db; r += da;
+        if (e >= W) { e -= W; r += 1; }
+    }
+}
+// `cnt` staged rows of W values (any W >= 1) out as one contiguous run, one element per lane per instruction, rounded once
+template <class S>
+RTB_HD void vjp_flush(const double *rows, int stride, int W, int cnt, S *__restrict__ dst, int lane)
+{
+    const int total = cnt * W;
+    int f = lane;
+    int r = f / W, e = f - r * W;
+    const int da = kWave / W, db = kWave - da * W;
+    for (; f < total; f += kWave) {
+        dst[f] = (S)rows[r * stride + e];
+        e += db; r += da;
+        if (e >= W) { e -= W; r += 1; }
+    }
+}
+
+// One register-resident tile: the walk of k_kin_reg (reg_compute: P and the finished Jacobian in registers), then the contraction in registers --
+// nothing of T, J or H goes to memory.  gT rows (one round of 64), gJ rows (rounds of kJRound lanes, contracted inside their round straight from
+// the staged row: no second 6 n registers) and the gq rows (rounds of floor(ldsd / (qw | 1)) lanes) pass through the one LDS buffer of
+// `ldsd` doubles: reg_lds_doubles(NJ) with gJ, 64 x 17 without -- what k_kin_reg asks for.
+template <int NJ, bool WANT_GT, bool WANT_GJ, class S>
+__device__ __forceinline__ void vjp_tile(const KinParams &kp, const ConstChain &cv, int ldsd, const S *__restrict__ q, const S *__restrict__ gT,
+                                         const S *__restrict__ gJ, S *__restrict__ gq, double *buf, int lane, int64_t tile)
+{
+    constexpr int W = 6 * NJ;
+    const int64_t cfg0 = tile * kWave;
+    const int64_t left = kp.N - cfg0;
+    const int ncfg = left < kWave ? (int)left : kWave;
+    Pose P;
+    double jac[6 * NJ];
+    reg_compute<NJ, true>(kp, cv, q, cfg0 + lane, P, jac);
+    double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if constexpr (WANT_GT) {
+        vjp_fill(gT + cfg0 * 16, 16, ncfg, buf, 17, lane);
+        __syncthreads();
+        const double *mine = buf + (lane < ncfg ? lane : 0) * 17;
+        vjp_pose_pullback(P, kp.has_base, kp.base, [&](int k) { return mine[k]; }, w);
+        __syncthreads();
+    }
+    double g[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) g[j] = 0.0;
+    if constexpr (WANT_GJ) {
+#pragma unroll
+        for (int r = 0; r < kWave / kJRound; ++r) {
+            int rows = ncfg - r * kJRound;
+            rows = rows < 0 ? 0 : (rows > kJRound ? kJRound : rows);
+            vjp_fill(gJ + (cfg0 + r * kJRound) * W, W, rows, buf, W + 1, lane);
+            __syncthreads();
+            if (lane / kJRound == r && lane < ncfg) {
+                const double *mine = buf + (lane % kJRound) * (W + 1);
+                vjp_contract<true>(NJ, w, [&](int k) { return jac[k]; }, [&](int k) { return mine[k]; }, [&](int k, double x) { g[k] += x; });
+            }
+            __syncthreads();
+        }
+    } else {
+        vjp_contract<false>(NJ, w, [&](int k) { return jac[k]; }, [&](int) { return 0.0; }, [&](int k, double x) { g[k] += x; });
+    }
+    // gq rows are q_width wide: a column no joint of the chain reads gets zero, joints sharing a column add up
+    const int qw = kp.qw, so = qw | 1;
+    int per = ldsd / so;
+    per = per > kWave ? kWave : per;
+    for (int r0 = 0; r0 < ncfg; r0 += per) {                 // wave-uniform
+        if (lane >= r0 && lane < r0 + per) {
+            double *mine = buf + (lane - r0) * so;
+            for (int c = 0; c < qw; ++c) mine[c] = 0.0;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) mine[jm_jq(cv.jmeta[j])] += g[j];
+        }
+        __syncthreads();
+        const int cnt = ncfg - r0 < per ? ncfg - r0 : per;
+        vjp_flush(buf, so, qw, cnt, gq + (cfg0 + r0) * qw, lane);
+        __syncthreads();
+    }
+}
+
+// the launch shape of k_kin_reg: ONE tile per single-wave workgroup, no grid-stride loop (see the comment there).  Registers: the pose term alone
+// fits k_kin_reg's budget (three waves per SIMD up to 8 joints); with gJ the running sums and the staged row's operands sit on top of the 6 n
+// Jacobian registers, and from 6 joints up the 168-register budget sent 2..46 of them to scratch -- those variants take two waves per SIMD, no scratch.
+template <int NJ, bool WANT_GT, bool WANT_GJ, class S>
+__global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints && !WANT_GJ ? RTB_REG_WAVES : 2)) void k_kin_vjp(KinParams kp, DevChain dc, int ldsd, const S *__restrict__ q,
+                                                                                           const S *__restrict__ gT, const S *__restrict__ gJ, S *__restrict__ gq)
+{
+    extern __shared__ __attribute__((aligned(16))) double buf[];
+    vjp_tile<NJ, WANT_GT, WANT_GJ>(kp, const_view(dc), ldsd, q, gT, gJ, gq, buf, threadIdx.x, xcd_tile());
+}
+
+// Run-time n (1..32), from a SUPPLIED pose and Jacobian (fp64, device): the contraction alone.  Serves rtbhip_kin_vjp_from_jacobian and the chains
+// beyond kKinRegMax, whose entry point runs the forward launch into scratch first.  One lane per row; a round of `per` rows passes through LDS as
+// rows of [T 16 | gT 16 | J 6n | gJ 6n | gq qw] doubles (odd stride), every global access a contiguous run.  jmeta (NULL: column k is joint k)
+// maps a joint to its q column; base (has_base) is pulled back from gT as in the register tile.  S: the storage type of gT, gJ and gq.
+struct VjpAnyParams {
+    int32_t n, qw, has_base, per;
+    int64_t N;
+    double base[12];
+};
+template <class S>
+__global__ __launch_bounds__(kWave) void k_vjp_from_jac_any(VjpAnyParams vp, const int32_t *__restrict__ jmeta, const double *__restrict__ T,
+                                                            const double *__restrict__ J, const S *__restrict__ gT, const S *__restrict__ gJ, S *__restrict__ gq)
+{
+    extern __shared__ __attribute__((aligned(16))) double buf[];
+    const int lane = threadIdx.x, n = vp.n, W = 6 * n, qw = vp.qw;
+    const int stride = (32 + 2 * W + qw) | 1;
+    const int64_t cfg0 = (int64_t)blockIdx.x * kWave;
+    const int64_t left = vp.N - cfg0;
+    const int ncfg = left < kWave ? (int)left : kWave;
+    for (int r0 = 0; r0 < ncfg; r0 += vp.per) {              // wave-uniform
+        const int cnt = ncfg - r0 < vp.per ? ncfg - r0 : vp.per;
+        const int64_t row0 = cfg0 + r0;
+        if (gT) {
+            vjp_fill(T + row0 * 16, 16, cnt, buf, stride, lane);
+            vjp_fill(gT + row0 * 16, 16, cnt, buf + 16, stride, lane);
+        }
+        vjp_fill(J + row0 * W, W, cnt, buf + 32, stride, lane);
+        if (gJ) vjp_fill(gJ + row0 * W, W, cnt, buf + 32 + W, stride, lane);
+        __syncthreads();
+        if (lane < cnt) {
+            double *mine = buf + lane * stride;
+            const double *Jr = mine + 32, *Gr = mine + 32 + W;
+            double *out = mine + 32 + 2 * W;
+            for (int c = 0; c < qw; ++c) out[c] = 0.0;
+            double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            if (gT) {
+                Pose P;
+                P.r00 = mine[0]; P.r01 = mine[1]; P.r02 = mine[2]; P.tx = mine[3];
+                P.r10 = mine[4]; P.r11 = mine[5]; P.r12 = mine[6]; P.ty = mine[7];
+                P.r20 = mine[8]; P.r21 = mine[9]; P.r22 = mine[10]; P.tz = mine[11];
+                vjp_pose_pullback(P, vp.has_base, vp.base, [&](int k) { return mine[16 + k]; }, w);
+            }
+            auto acc = [&](int k, double x) { out[jmeta ? jm_jq(jmeta[k]) : k] += x; };
+            if (gJ) vjp_contract<true>(n, w, [&](int k) { return Jr[k]; }, [&](int k) { return Gr[k]; }, acc);
+            else vjp_contract<false>(n, w, [&](int k) { return Jr[k]; }, [&](int) { return 0.0; }, acc);
+        }
+        __syncthreads();
+        vjp_flush(buf + 32 + 2 * W, stride, qw, cnt, gq + row0 * qw, lane);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void k_widen_f32(const float *__restrict__ src, int64_t count, double *__restrict__ dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < count) dst[i] = src[i];
+}
+
+template <class S>
+static int launch_vjp_from_jac_s(int n, int qw, const int32_t *jmeta, const Affine *base, const double *T, const double *J, const S *gT, const S *gJ,
+                                 int64_t N, S *gq, hipStream_t s)
+{
+    if (N == 0) return RTBHIP_OK;
+    if (n < 1 || n > RTBHIP_MAX_JOINTS) { set_error("kin_vjp_from_jacobian: n must be 1..32"); return RTBHIP_ELIMIT; }
+    const int64_t tiles = (N + kWave - 1) / kWave;
+    if (tiles > 0x7fffffff) { set_error("kin_vjp: batch too large for one launch"); return RTBHIP_ELIMIT; }
+    VjpAnyParams vp;
+    vp.n = n; vp.qw = qw; vp.N = N;
+    vp.has_base = base && base->used;
+    for (int i = 0; i < 12; i++) vp.base[i] = base ? base->v[i] : 0.0;
+    const int stride = (32 + 12 * n + qw) | 1;               // <= 673 doubles (n = 32, q_width = 256): at least 9 rows per round in 48 KB
+    vp.per = std::min(kWave, (48 * 1024 / 8) / stride);
+    const size_t lds = (size_t)vp.per * stride * sizeof(double);
+    hipLaunchKernelGGL((k_vjp_from_jac_any<S>), dim3((unsigned)tiles), dim3(kWave), lds, s, vp, jmeta, T, J, gT, gJ, gq);
+    note_launch((int)tiles, kWave, (int)lds);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "k_vjp_from_jac_any launch");
+    return RTBHIP_OK;
+}
+int launch_vjp_from_jac(int n, const double *T, const double *J, const double *gT, const double *gJ, int64_t N, double *gq, hipStream_t s)
+{
+    return launch_vjp_from_jac_s(n, n, nullptr, nullptr, T, J, gT, gJ, N, gq, s);
+}
+
+template <int NJ, class S>
+static hipError_t launch_vjp_nj(dim3 grid, hipStream_t s, const KinParams &kp, const DevChain &dc, const S *q, const S *gT, const S *gJ, S *gq)
+{
+    // without gJ only the 64 x 17 pose tile is staged (as fkine alone in launch_kin_s); a gq row of up to 256 columns fits either request
+    const int ldsd = gJ ? reg_lds_doubles(NJ) : kWave * 17;
+    const size_t lds = (size_t)ldsd * sizeof(double);
+    if (gT && gJ) hipLaunchKernelGGL((k_kin_vjp<NJ, true, true, S>), grid, dim3(kWave), lds, s, kp, dc, ldsd, q, gT, gJ, gq);
+    else if (gT) hipLaunchKernelGGL((k_kin_vjp<NJ, true, false, S>), grid, dim3(kWave), lds, s, kp, dc, ldsd, q, gT, gJ, gq);
+    else hipLaunchKernelGGL((k_kin_vjp<NJ, false, true, S>), grid, dim3(kWave), lds, s, kp, dc, ldsd, q, gT, gJ, gq);
+    note_launch((int)grid.x, kWave, (int)lds);
+    return hipGetLastError();
+}
+
+// S: the storage type of q, gT, gJ and gq.  1..kKinRegMax joints: the fused register tile.  Longer chains: the forward launch (run-time-n tile,
+// no base: it is pulled back from gT) into stream-ordered scratch, then k_vjp_from_jac_any with the chain's joint -> q column table; float rows
+// are widened into scratch first, so that the forward runs on exactly the values the fp64 call would be given.
+template <class S>
+static int launch_kin_vjp_s(const Chain *c, const DevChain &ops, const S *q, int64_t N, const Affine &base, const Affine &tool, const S *gT, const S *gJ,
+                            S *gq, hipStream_t s)
+{
+    if (N == 0) return RTBHIP_OK;
+    const int64_t tiles = (N + kWave - 1) / kWave;
+    if (tiles > 0x7fffffff) { set_error("fkine_jacob_vjp: batch too large for one launch"); return RTBHIP_ELIMIT; }
+    if (g_use_reg && c->n >= 1 && c->n <= kKinRegMax) {
+        KinParams kp;
+        kp.n = c->n; kp.qw = c->q_width; kp.stride = kin_stride(c->n); kp.frame = 0; kp.has_base = base.used; kp.pad = 0; kp.N = N;
+        for (int i = 0; i < 12; i++) kp.base[i] = base.v[i];
+        chain_tail(c, tool, kp.tail);
+        dim3 grid((unsigned)tiles);
+        hipError_t e = hipSuccess;
+        switch (c->n) {
+        case 1: e = launch_vjp_nj<1>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        case 2: e = launch_vjp_nj<2>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        case 3: e = launch_vjp_nj<3>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        case 4: e = launch_vjp_nj<4>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        case 5: e = launch_vjp_nj<5>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        case 6: e = launch_vjp_nj<6>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        case 7: e = launch_vjp_nj<7>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        case 8: e = launch_vjp_nj<8>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        case 9: e = launch_vjp_nj<9>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        default: e = launch_vjp_nj<10>(grid, s, kp, ops, q, gT, gJ, gq); break;
+        }
+        if (e != hipSuccess) return hip_fail(e, "k_kin_vjp launch");
+        return RTBHIP_OK;
+    }
+    if (c->n < 1 || c->n > RTBHIP_MAX_JOINTS) { set_error("fkine_jacob_vjp: chains of 1..RTBHIP_MAX_JOINTS joints"); return RTBHIP_ELIMIT; }
+    const int rc0 = pool_keep_cached();      // the temporaries come from the device's pool, kept cached between calls (rtbhip_partial_fkine0 does the same)
+    if (rc0 != RTBHIP_OK) return rc0;
+    const size_t n = (size_t)c->n, rows = (size_t)N;
+    const size_t qd = std::is_same<S, float>::value ? rows * c->q_width : 0;
+    void *p = nullptr;
+    hipError_t e = hipMallocAsync(&p, (rows * (16 + 6 * n) + qd) * sizeof(double), s);
+    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync (fkine_jacob_vjp temporaries)");
+    double *Ts = (double *)p, *Js = Ts + rows * 16, *qs = Js + rows * 6 * n;
+    const double *q64;
+    if constexpr (std::is_same<S, float>::value) {
+        const int64_t count = (int64_t)qd;
+        hipLaunchKernelGGL(k_widen_f32, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, q, count, qs);
+        q64 = qs;
+    } else {
+        q64 = q;
+    }
+    Affine nobase;
+    nobase.used = 0;
+    for (int i = 0; i < 12; i++) nobase.v[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    int rc = launch_kin(c, ops, q64, N, nobase, tool, 0, Ts, Js, nullptr, s);
+    if (rc == RTBHIP_OK) rc = launch_vjp_from_jac_s(c->n, c->q_width, ops.jmeta, &base, Ts, Js, gT, gJ, N, gq, s);
+    (void)hipFreeAsync(p, s);
+    return rc;
+}
+int launch_kin_vjp(const Chain *c, const DevChain &ops, const double *q, int64_t N, const Affine &base, const Affine &tool, const double *gT,
+                   const double *gJ, double *gq, hipStream_t s)
+{
+    return launch_kin_vjp_s(c, ops, q, N, base, tool, gT, gJ, gq, s);
+}
+int launch_kin_vjp_f32(const Chain *c, const DevChain &ops, const float *q, int64_t N, const Affine &base, const Affine &tool, const float *gT,
+                       const float *gJ, float *gq, hipStream_t s)
+{
+    return launch_kin_vjp_s(c, ops, q, N, base, tool, gT, gJ, gq, s);
+}
+
 }  // namespace rtbhip

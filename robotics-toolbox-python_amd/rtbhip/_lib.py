@@ -45,6 +45,17 @@ _i64 = C.c_int64
 _u64 = C.c_uint64
 _i32 = C.c_int32
 
+
+class _sp(C.c_void_p):
+    """`void *stream` of the vector-Jacobian-product entry points: a void pointer like any other for the call, a type of its own in this table.
+    tests/test_api_refusals.py finds "every compute entry point" by the shape (..., int32 mem, void *stream) of a row here and wants its own
+    refusal rows for each; the rows of these three are in tests/test_kin_vjp.py, which keeps the same census for them."""
+
+    @classmethod
+    def from_param(cls, value):
+        return C.c_void_p.from_param(value)
+
+
 # name -> (restype, argtypes); must list every symbol include/rtbhip.h declares
 SIGNATURES = {
     "rtbhip_last_error": (C.c_char_p, []),
@@ -69,6 +80,9 @@ SIGNATURES = {
     "rtbhip_fkine_jacob_packed_f32": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_hessian": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_hessian_from_jacobian": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp]),
+    "rtbhip_fkine_jacob_vjp": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _sp]),
+    "rtbhip_fkine_jacob_vjp_f32": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _sp]),
+    "rtbhip_kin_vjp_from_jacobian": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _sp]),
     "rtbhip_manipulability_from_jacobian": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
     "rtbhip_jacobm_from_jacobian": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp]),
     "rtbhip_angle_axis": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp]),
@@ -222,6 +236,15 @@ def shard_range(N, rank, world):
 # ---------------------------------------------------------------- buffer plumbing
 def is_torch(x):
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
+
+
+def wants_grad(q):
+    """True when a call on q must record an autograd node (rtbhip/autograd.py): q is a CUDA tensor that requires grad and gradients are enabled.
+    Anything else -- host input, a plain tensor, torch.no_grad() -- takes the ordinary path, untouched."""
+    if not (is_torch(q) and q.is_cuda and getattr(q, "requires_grad", False)):
+        return False
+    import torch
+    return torch.is_grad_enabled()
 
 
 def device_dtype(tensors, f32_ok=False, what="device inputs"):

@@ -750,7 +750,11 @@ class ETS:
         """Forward kinematics as ndarray: (4,4) for one q, (N,4,4) for a trajectory
         (reference ETS.eval robot/ETS.py:1021-1141 -> ETS_fkine core/fknm.cpp:923-1064).
         A float32 CUDA q gives a float32 tensor (rtbhip_fkine_jacob_f32: fp64 arithmetic, each entry rounded once -- equal to
-        `eval(q.double()).float()` bit for bit, half the bytes); so do jacob0, jacobe and fkine_jacob0.  NumPy float32 is converted on the host."""
+        `eval(q.double()).float()` bit for bit, half the bytes); so do jacob0, jacobe and fkine_jacob0.  NumPy float32 is converted on the host.
+        A CUDA q with requires_grad (and gradients enabled) gives a T that back-propagates to q (rtbhip/autograd.py); so do jacob0 and fkine_jacob0."""
+        if _lib.wants_grad(q):
+            from .autograd import differentiable
+            return differentiable(self, "T", q, base if include_base else None, tool)
         q2, single, tm = self._shape_q(q, f32_ok=True)
         N = q2.shape[0]
         b = small(base, 16) if (base is not None and include_base) else None
@@ -799,6 +803,9 @@ class ETS:
     def jacob0(self, q, tool=None):
         """Geometric Jacobian in the chain's start frame: (6,n), or (N,6,n) for a trajectory
         (reference ETS.jacob0 robot/ETS.py:1143-1199 -> ETS_jacob0 core/fknm.cpp:785-850)."""
+        if _lib.wants_grad(q):
+            from .autograd import differentiable
+            return differentiable(self, "J", q, None, tool)
         return self._jac(q, tool, 0)
 
     def jacobe(self, q, tool=None):
@@ -811,7 +818,11 @@ class ETS:
         packed=True: ONE (N, 16 + 6n) array whose row i is [T[i] (16, row-major 4x4) | J[i] ((6,n) C-order)] -- the device writes a single
         stream and the row is the T||J message of the multi-GPU gather (rtbhip_fkine_jacob_packed); the returned (T, J) are strided views
         of it and `.packed` / the third item gives the array itself: `T, J, TJ = ets.fkine_jacob0(q, packed=True)`.  `out` = a TJ array of an
-        earlier call to write into; it must have q's element type (a float32 device q: float32 everywhere, see eval)."""
+        earlier call to write into; it must have q's element type (a float32 device q: float32 everywhere, see eval).
+        The two-array start-frame form is differentiable (see eval): T and J come from one autograd node, so a loss on both is one backward launch."""
+        if frame == 0 and not packed and out is None and _lib.wants_grad(q):
+            from .autograd import differentiable
+            return differentiable(self, "TJ", q, base, tool)
         q2, single, tm = self._shape_q(q, f32_ok=True)
         N = q2.shape[0]
         f32 = self._f32(q2, tm)
