@@ -451,6 +451,7 @@ int rtbhip_last_launch(int32_t *grid, int32_t *block, int32_t *lds_bytes);
  *                             rtbhip_jit_* below) / always the general kernel -- the same bits either way
  *   "rne_sig", "tree_sig" 1 | 0   the same switch for the dynamics kernels: a DH link table (built in: Panda, Puma560) / a link tree (built in: UR3 / 5 / 10, the
  *                             Interbotix arms, Fetch, Mico, any serial arm of up to 8 revolute joints); every other robot: its run-time instantiation
+ *   "kin_sig" 1 | 0           the same switch for fkine / jacob0 / jacobe and their fused and packed forms (built in: Panda, UR; calls without a tool)
  * Others: "coalesced", "reg", "tiles_per_wave", "hess_mode" (fkine / Jacobian / Hessian store paths), "rne_tiles_per_wave",
  *         "partial3" 1 | 0 (order-3 partial_fkine0 on workgroups that own whole configurations / on the general kernel),
  *         "partial3_fused" 1 | 0 (that kernel forms the Hessians from the Jacobians it stages / reads a Hessian tensor written by a launch of its own),

@@ -85,6 +85,8 @@ constexpr SegSig kIkSigPandaURDF = kSegSigPresent | seg_sig_of(0, kSegIdentity, 
 //   Universal Robots UR3 / UR5 / UR10 from their URDFs (ur_description, to tool0): six joints, one signature for the three sizes.
 constexpr SegSig kIkSigUR = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegGeneral, 2) | seg_sig_of(2, kSegIdentity, 5) | seg_sig_of(3, kSegRzP, 1) |
                             seg_sig_of(4, kSegPermA, 4) | seg_sig_of(5, kSegPermB, 4) | seg_sig_of(6, kSegGeneral, 4);
+// (k_kin_reg is instantiated for the same three: kin_reg.h holds them as kSig*, one definition for both files to agree with)
+static_assert(kIkSigPandaETS == kSigPandaETS && kIkSigPandaURDF == kSigPandaURDF && kIkSigUR == kSigUR, "the built-in signatures of k_ik and k_kin_reg are the same robots");
 static int g_ik_sig = 1;          // rtbhip_tune("ik_sig", 0): never take a signature's instantiation (A/B, tests)
 template <int NJ, int STEP, int AUX = 0, SegSig SIG = 0>
 __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints && !(STEP & kIkStepNull) ? RTB_IK_WAVES : 1)) void k_ik(IkDev p, DevChain dc, const double *qlim_g, const double *__restrict__ Tep,

@@ -166,6 +166,17 @@ RTB_HD void pose_mul_seg(Pose &P, const CV &cv, int j)
 //   Rx / Ry / Rz  rotation about one axis, the two other columns mix                                                      12
 //   ..P / ..N     the quarter turns (off-diagonal +-1; the diagonal keeps its cos(pi/2))                                  9 (3 mul, 3 add, 3 fma)
 //   permA / permB the cyclic column permutations of the axis conjugation: register moves                                 0
+// a chain view may carry a pointer to the sincos constants (k_ik: see sincos_reduced_tab in trig.h); the others use the literals
+template <class CV, class = void> struct cv_has_trig { static constexpr bool value = false; };
+template <class CV> struct cv_has_trig<CV, decltype((void)(((const CV *)nullptr)->trig))> { static constexpr bool value = true; };
+// ... or ask for the fused-chain translation  t += R c  (pose_t3_fma: the form every structured segment product is an instance of) without carrying the
+// sincos table: k_kin_diff's views (diff_kernel.h), so that its structure instantiations return its general kernel's bits
+template <class CV, class = void> struct cv_t3fma { static constexpr bool value = false; };
+template <class CV> struct cv_t3fma<CV, typename CV::t3fma_tag> { static constexpr bool value = true; };
+// What a chain view's GENERAL walk does with a segment's translation decides what its structure instantiations must do with it:
+//   fused     t <- fma(z, R.2, fma(y, R.1, fma(x, R.0, t)))        (pose_t3_fma: k_ik's plain walk, k_kin_diff)
+//   unfused   t <- t + fma(z, R.2, fma(y, R.1, round(x R.0)))      (pose_t3: k_kin_reg, the fused fkine + Jacobian headline -- its bits are pinned)
+template <class CV> struct cv_fused_translation { static constexpr bool value = cv_has_trig<CV>::value || cv_t3fma<CV>::value; };
 template <int TM, class CV>
 RTB_HD void pose_seg_translate(Pose &P, const CV &cv, int j)
 {
@@ -178,12 +189,38 @@ RTB_HD void pose_seg_rotate(Pose &P, const CV &cv, int j)
 {
     pose_rot_const<CLS>(P, [&](int k) { return cv.seg[j].r[k]; });      // entries whose kind is not kAny are never read
 }
-// compile-time class and translation mask: straight-line code (k_ik's instantiations for known robots: ik_kernels.hip, kIkSig*)
+// the unfused form: the dot product of pose_t3 with the terms of the exactly-zero components dropped (exactform.h: dotk), then the one addition.
+// A segment without a translation adds nothing: the general product adds a zero there, which changes no finite value (only a -0 would become +0;
+// the walk's translations are sums that start from +0 or a non-zero constant -- tests/test_kin_sig_emu.py replays both forms on the zeros).
+template <int TM, class CV>
+RTB_HD void pose_seg_translate_sum(Pose &P, const CV &cv, int j)
+{
+#pragma clang fp contract(off)
+    if (TM == 0) return;
+    constexpr int KX = (TM & 1) ? kCA : kC0, KY = (TM & 2) ? kCA : kC0, KZ = (TM & 4) ? kCA : kC0;
+    const double x = (TM & 1) ? cv.seg[j].t[0] : 0.0, y = (TM & 2) ? cv.seg[j].t[1] : 0.0, z = (TM & 4) ? cv.seg[j].t[2] : 0.0;
+    const double ax = dotk<KX, KY, KZ>(x, P.r00, y, P.r01, z, P.r02);
+    const double ay = dotk<KX, KY, KZ>(x, P.r10, y, P.r11, z, P.r12);
+    const double az = dotk<KX, KY, KZ>(x, P.r20, y, P.r21, z, P.r22);
+    P.tx = P.tx + ax; P.ty = P.ty + ay; P.tz = P.tz + az;
+}
+// Classes that take the GENERAL product inside an unfused signature kernel: the two column permutations.  Their structured form is nine register
+// moves, and a move carries a -0 where the general product's  0 y + 1 x + 0 z  returns +0 (unless y and z are negative too): on rows with exact
+// zeros (q_j = 0) the UR arms' poses and Jacobians came out with the other sign of zero in about 4 % of such rows (host replay, 60 000 rows of
+// zeros, quarter and half turns; tests/test_kin_sig_emu.py).  The quarter turns, single-axis rotations and the identity showed none, on either Panda
+// or on the UR.  (k_ik and k_kin_diff compare values, not signs of zeros: their fused forms keep the moves.)
+#ifndef RTB_SIG_UNFUSED_GENERAL
+#define RTB_SIG_UNFUSED_GENERAL ((1u << kSegPermA) | (1u << kSegPermB))
+#endif
+// compile-time class and translation mask: straight-line code (the instantiations for known robots: kin_reg.h, kSig*).  Each view gets the
+// specialisation of ITS general product (cv_fused_translation), so that a signature kernel returns its general kernel's bits.
 template <int CLS, int TM, class CV>
 RTB_HD void pose_mul_seg_sig(Pose &P, const CV &cv, int j)
 {
-    if (CLS == kSegGeneral) { pose_mul_seg<true>(P, cv, j); return; }
-    pose_seg_translate<TM>(P, cv, j);
+    constexpr bool FUSED = cv_fused_translation<CV>::value;
+    if (CLS == kSegGeneral || (!FUSED && ((RTB_SIG_UNFUSED_GENERAL >> CLS) & 1))) { pose_mul_seg<FUSED>(P, cv, j); return; }
+    if constexpr (FUSED) pose_seg_translate<TM>(P, cv, j);
+    else pose_seg_translate_sum<TM>(P, cv, j);
     pose_seg_rotate<CLS>(P, cv, j);
 }
 // run-time class (a wave-uniform switch on the descriptor): measured SLOWER than the general product inside k_ik (round 5 visit c: config 3

@@ -116,7 +116,8 @@ __global__ __launch_bounds__(kWave) void k_kin_f32(KinParams kp, DevChain dc, co
 #define RTB_REG_WAVES 3   // waves per SIMD the register allocator must leave room for (<= 168 VGPRs)
 #endif
 // One register-resident tile (64 configurations) of a chain with NJ joints; shared by k_kin_reg and k_fleet.
-template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false, class S>
+// SIG != 0: the chain's structure signature (kin_reg.h) -- the walk is straight-line code specialised for the robot's constants (k_fleet: always 0)
+template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false, SegSig SIG = 0, class S>
 __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &cv, const S *__restrict__ q,
                                          S *__restrict__ T, S *__restrict__ J, double *buf, int lane,
                                          int64_t tile)
@@ -127,7 +128,7 @@ __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &
     const int ncfg = left < kWave ? (int)left : kWave;
     Pose P;
     double jac[6 * NJ];
-    reg_compute<NJ, WANT_J>(kp, cv, q, cfg0 + lane, P, jac);
+    reg_compute<NJ, WANT_J, SIG>(kp, cv, q, cfg0 + lane, P, jac);
     if constexpr (PACKED) {
         // T is the packed (N, 16 + W) array: rounds of kPRound lanes stage [T | J] and the wave writes the round's rows as one contiguous run
         static_assert(!PACKED || (WANT_T && WANT_J), "packed rows carry both");
@@ -176,21 +177,25 @@ __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &
 // ONE tile per single-wave workgroup, no grid-stride loop: with a loop LICM hoists every segment's
 // (loop-invariant) scalar loads into the preheader, where they overflow the SGPR file and come back
 // as v_readlane pairs on each use.  The dispatcher balances the tiles instead.
-template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false>
+// SIG != 0 (launch_reg: a built-in signature, no tool): every segment product is the exact specialisation of the general kernel's UNFUSED product
+// for that segment's zeros and ones (kin_device.h: pose_mul_seg_sig, pose_seg_translate_sum) -- the same bits from fewer instructions, no 12-double
+// segment loads, no descriptor branches, no fences; the q loads are issued together.  What that can buy is the launch's ramp, not its steady state,
+// which the stores set (executed instruction counts, the N sweep and the A/B pairs: profiles/r07_kin_sig.txt).
+template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false, SegSig SIG = 0>
 __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints ? RTB_REG_WAVES : 2)) void k_kin_reg(KinParams kp, DevChain dc, const double *__restrict__ q,
                                                   double *__restrict__ T, double *__restrict__ J)
 {
     extern __shared__ __attribute__((aligned(16))) double buf[];
     // (the packed form writes ~30 KB runs per wave: like the Hessian tile it may prefer the identity mapping -- RTB_PACKED_XCD, A/B'd in profiles/r05_*)
-    reg_tile<NJ, WANT_T, WANT_J, PACKED>(kp, const_view(dc), q, T, J, buf, threadIdx.x, (PACKED && !RTB_PACKED_XCD) ? blockIdx.x : xcd_tile());
+    reg_tile<NJ, WANT_T, WANT_J, PACKED, SIG>(kp, const_view(dc), q, T, J, buf, threadIdx.x, (PACKED && !RTB_PACKED_XCD) ? blockIdx.x : xcd_tile());
 }
 // float32 q, T, J (PACKED: [T | J] rows): the same tile, the same launch shape; only the widths of the row accesses differ (kin_tile.h)
-template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false>
+template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false, SegSig SIG = 0>
 __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints ? RTB_REG_WAVES : 2)) void k_kin_reg_f32(KinParams kp, DevChain dc, const float *__restrict__ q,
                                                       float *__restrict__ T, float *__restrict__ J)
 {
     extern __shared__ __attribute__((aligned(16))) double buf[];
-    reg_tile<NJ, WANT_T, WANT_J, PACKED>(kp, const_view(dc), q, T, J, buf, threadIdx.x, (PACKED && !RTB_PACKED_XCD) ? blockIdx.x : xcd_tile());
+    reg_tile<NJ, WANT_T, WANT_J, PACKED, SIG>(kp, const_view(dc), q, T, J, buf, threadIdx.x, (PACKED && !RTB_PACKED_XCD) ? blockIdx.x : xcd_tile());
 }
 
 static int g_hess_mode = 0;   // A/B knob (rtbhip_tune "hess_mode")
@@ -546,6 +551,7 @@ namespace {
 int g_coalesced = 1;   // tuning knobs (rtbhip_tune)
 int g_tiles_per_wave = 1;
 int g_use_reg = 1;
+int g_kin_sig = 1;     // rtbhip_tune("kin_sig", 0): k_kin_reg never takes a structure signature's instantiation (A/B, tests)
 }  // namespace
 
 void kin_tune(const char *key, int value)
@@ -556,6 +562,7 @@ void kin_tune(const char *key, int value)
     if (k == "reg") g_use_reg = value;
     if (k == "hess_mode") g_hess_mode = value;
     if (k == "diff_sig") g_diff_sig = value != 0;
+    if (k == "kin_sig") g_kin_sig = value != 0;
 }
 
 template <bool WT, bool WJ, bool WH, class S>
@@ -588,36 +595,63 @@ static hipError_t launch_variant(bool coalesced, dim3 grid, size_t lds, hipStrea
     return hipGetLastError();
 }
 
-template <int NJ>
-static hipError_t launch_reg(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc,
-                             const double *q, double *T, double *J)
+// The signature of a chain that k_kin_reg has a built-in instantiation for (kin_reg.h: kSig*), else 0.  A tool is folded into the tail on the host
+// (chain_tail) while a signature's last segment is the table's own: with a tool the general kernel serves.  A base is applied at staging: no matter.
+static SegSig kin_reg_sig(const Chain *c, const Affine &tool)
 {
-    if (T && J) hipLaunchKernelGGL((k_kin_reg<NJ, true, true>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
-    else if (T) hipLaunchKernelGGL((k_kin_reg<NJ, true, false>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
-    else hipLaunchKernelGGL((k_kin_reg<NJ, false, true>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
+    if (!g_kin_sig || tool.used || c->n < 6 || c->n > 7 || !jit_builtin_enabled()) return 0;
+    for (int j = 0; j < c->n; ++j)
+        if (jm_prismatic(c->jmeta[j]) || jm_flip(c->jmeta[j])) return 0;
+    const SegSig sig = chain_signature(c->jmeta.data(), c->n);
+    if (c->n == 7 && (sig == kSigPandaETS || sig == kSigPandaURDF)) return sig;
+    if (c->n == 6 && sig == kSigUR) return sig;
+    return 0;
+}
+// S = double: k_kin_reg, S = float: k_kin_reg_f32
+template <int NJ, bool WT, bool WJ, bool PACKED, SegSig SIG, class S>
+static void launch_reg_one(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const S *q, S *T, S *J)
+{
+    if constexpr (sizeof(S) == 8) hipLaunchKernelGGL((k_kin_reg<NJ, WT, WJ, PACKED, SIG>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
+    else hipLaunchKernelGGL((k_kin_reg_f32<NJ, WT, WJ, PACKED, SIG>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
+}
+template <int NJ, SegSig SIG, class S>
+static hipError_t launch_reg_sig(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const S *q, S *T, S *J)
+{
+    if (T && J) launch_reg_one<NJ, true, true, false, SIG>(grid, lds, s, kp, dc, q, T, J);
+    else if (T) launch_reg_one<NJ, true, false, false, SIG>(grid, lds, s, kp, dc, q, T, J);
+    else launch_reg_one<NJ, false, true, false, SIG>(grid, lds, s, kp, dc, q, T, J);
     return hipGetLastError();
 }
-template <int NJ>
-static hipError_t launch_reg(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc,
-                             const float *q, float *T, float *J)
+template <int NJ, class S>
+static hipError_t launch_reg(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const S *q, S *T, S *J, SegSig sig)
 {
-    if (T && J) hipLaunchKernelGGL((k_kin_reg_f32<NJ, true, true>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
-    else if (T) hipLaunchKernelGGL((k_kin_reg_f32<NJ, true, false>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
-    else hipLaunchKernelGGL((k_kin_reg_f32<NJ, false, true>), grid, dim3(kWave), lds, s, kp, dc, q, T, J);
-    return hipGetLastError();
+    if constexpr (NJ == 7) {
+        if (sig == kSigPandaETS) return launch_reg_sig<7, kSigPandaETS>(grid, lds, s, kp, dc, q, T, J);
+        if (sig == kSigPandaURDF) return launch_reg_sig<7, kSigPandaURDF>(grid, lds, s, kp, dc, q, T, J);
+    }
+    if constexpr (NJ == 6) {
+        if (sig == kSigUR) return launch_reg_sig<6, kSigUR>(grid, lds, s, kp, dc, q, T, J);
+    }
+    return launch_reg_sig<NJ, 0>(grid, lds, s, kp, dc, q, T, J);
 }
 
-template <int NJ>
-static hipError_t launch_reg_packed(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const double *q, double *TJ)
+template <int NJ, SegSig SIG, class S>
+static hipError_t launch_reg_packed_sig(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const S *q, S *TJ)
 {
-    hipLaunchKernelGGL((k_kin_reg<NJ, true, true, true>), grid, dim3(kWave), lds, s, kp, dc, q, TJ, (double *)nullptr);
+    launch_reg_one<NJ, true, true, true, SIG>(grid, lds, s, kp, dc, q, TJ, (S *)nullptr);
     return hipGetLastError();
 }
-template <int NJ>
-static hipError_t launch_reg_packed(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const float *q, float *TJ)
+template <int NJ, class S>
+static hipError_t launch_reg_packed(dim3 grid, size_t lds, hipStream_t s, const KinParams &kp, const DevChain &dc, const S *q, S *TJ, SegSig sig)
 {
-    hipLaunchKernelGGL((k_kin_reg_f32<NJ, true, true, true>), grid, dim3(kWave), lds, s, kp, dc, q, TJ, (float *)nullptr);
-    return hipGetLastError();
+    if constexpr (NJ == 7) {
+        if (sig == kSigPandaETS) return launch_reg_packed_sig<7, kSigPandaETS>(grid, lds, s, kp, dc, q, TJ);
+        if (sig == kSigPandaURDF) return launch_reg_packed_sig<7, kSigPandaURDF>(grid, lds, s, kp, dc, q, TJ);
+    }
+    if constexpr (NJ == 6) {
+        if (sig == kSigUR) return launch_reg_packed_sig<6, kSigUR>(grid, lds, s, kp, dc, q, TJ);
+    }
+    return launch_reg_packed_sig<NJ, 0>(grid, lds, s, kp, dc, q, TJ);
 }
 
 // rtbhip_fkine_jacob_packed: rows [T (16, base applied) | J (6n)] of ONE (N, 16 + 6n) array -- a single write stream (SURVEY 8e's T||J message)
@@ -637,18 +671,19 @@ static int launch_kin_packed_s(const Chain *c, const DevChain &ops, const S *q, 
     dim3 grid((unsigned)tiles);
     if (g_use_reg && c->n >= 1 && c->n <= kKinRegMax) {
         const size_t rl = (size_t)reg_lds_doubles_packed(c->n) * sizeof(double);
+        const SegSig sig = kin_reg_sig(c, tool);
         hipError_t e = hipSuccess;
         switch (c->n) {
-        case 1: e = launch_reg_packed<1>(grid, rl, s, kp, ops, q, TJ); break;
-        case 2: e = launch_reg_packed<2>(grid, rl, s, kp, ops, q, TJ); break;
-        case 3: e = launch_reg_packed<3>(grid, rl, s, kp, ops, q, TJ); break;
-        case 4: e = launch_reg_packed<4>(grid, rl, s, kp, ops, q, TJ); break;
-        case 5: e = launch_reg_packed<5>(grid, rl, s, kp, ops, q, TJ); break;
-        case 6: e = launch_reg_packed<6>(grid, rl, s, kp, ops, q, TJ); break;
-        case 7: e = launch_reg_packed<7>(grid, rl, s, kp, ops, q, TJ); break;
-        case 8: e = launch_reg_packed<8>(grid, rl, s, kp, ops, q, TJ); break;
-        case 9: e = launch_reg_packed<9>(grid, rl, s, kp, ops, q, TJ); break;
-        default: e = launch_reg_packed<10>(grid, rl, s, kp, ops, q, TJ); break;
+        case 1: e = launch_reg_packed<1>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        case 2: e = launch_reg_packed<2>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        case 3: e = launch_reg_packed<3>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        case 4: e = launch_reg_packed<4>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        case 5: e = launch_reg_packed<5>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        case 6: e = launch_reg_packed<6>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        case 7: e = launch_reg_packed<7>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        case 8: e = launch_reg_packed<8>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        case 9: e = launch_reg_packed<9>(grid, rl, s, kp, ops, q, TJ, sig); break;
+        default: e = launch_reg_packed<10>(grid, rl, s, kp, ops, q, TJ, sig); break;
         }
         note_launch((int)grid.x, kWave, (int)rl);
         if (e != hipSuccess) return hip_fail(e, "k_kin_reg (packed) launch");
@@ -719,18 +754,19 @@ static int launch_kin_s(const Chain *c, const DevChain &ops, const S *q, int64_t
         grid = dim3((unsigned)tiles);
         // fkine alone stages only the 64 x 17 pose tile (8.7 KB): with the Jacobian's 32 x (6n + 1) rounds left out of the request more waves fit a CU
         const size_t rl = (size_t)(J ? reg_lds_doubles(c->n) : kWave * 17) * sizeof(double);
+        const SegSig sig = kin_reg_sig(c, tool);
         hipError_t e = hipSuccess;
         switch (c->n) {
-        case 1: e = launch_reg<1>(grid, rl, s, kp, ops, q, T, J); break;
-        case 2: e = launch_reg<2>(grid, rl, s, kp, ops, q, T, J); break;
-        case 3: e = launch_reg<3>(grid, rl, s, kp, ops, q, T, J); break;
-        case 4: e = launch_reg<4>(grid, rl, s, kp, ops, q, T, J); break;
-        case 5: e = launch_reg<5>(grid, rl, s, kp, ops, q, T, J); break;
-        case 6: e = launch_reg<6>(grid, rl, s, kp, ops, q, T, J); break;
-        case 7: e = launch_reg<7>(grid, rl, s, kp, ops, q, T, J); break;
-        case 8: e = launch_reg<8>(grid, rl, s, kp, ops, q, T, J); break;
-        case 9: e = launch_reg<9>(grid, rl, s, kp, ops, q, T, J); break;
-        default: e = launch_reg<10>(grid, rl, s, kp, ops, q, T, J); break;
+        case 1: e = launch_reg<1>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        case 2: e = launch_reg<2>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        case 3: e = launch_reg<3>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        case 4: e = launch_reg<4>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        case 5: e = launch_reg<5>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        case 6: e = launch_reg<6>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        case 7: e = launch_reg<7>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        case 8: e = launch_reg<8>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        case 9: e = launch_reg<9>(grid, rl, s, kp, ops, q, T, J, sig); break;
+        default: e = launch_reg<10>(grid, rl, s, kp, ops, q, T, J, sig); break;
         }
         note_launch((int)grid.x, kWave, (int)rl);
         if (e != hipSuccess) return hip_fail(e, "k_kin_reg launch");

@@ -60,6 +60,15 @@ inline SegSig chain_signature(const int32_t *jmeta, int n)      // host: from th
     for (int j = 0; j <= n; ++j) s |= seg_sig_of(j, jm_cls(jmeta[j]), jm_tmask(jmeta[j]));
     return s;
 }
+// Structure signatures k_kin_reg has straight-line instantiations for (kin_kernels.hip) -- the robots of k_ik's built-in list (ik_kernels.hip: kIkSig*,
+// which says where each comes from and asserts that the two lists agree).  A signature is a property of the robot's constants; the launcher compares
+// a chain's own with this list and falls back to the general kernel.
+constexpr SegSig kSigPandaETS = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegRxN, 0) | seg_sig_of(2, kSegRxP, 6) | seg_sig_of(3, kSegRxP, 1) |
+                                seg_sig_of(4, kSegRxN, 7) | seg_sig_of(5, kSegRxP, 0) | seg_sig_of(6, kSegRxP, 7) | seg_sig_of(7, kSegRz, 4);
+constexpr SegSig kSigPandaURDF = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegRxN, 0) | seg_sig_of(2, kSegRxP, 2) | seg_sig_of(3, kSegRxP, 1) |
+                                 seg_sig_of(4, kSegRxN, 3) | seg_sig_of(5, kSegRxP, 0) | seg_sig_of(6, kSegRxP, 1) | seg_sig_of(7, kSegRz, 4);
+constexpr SegSig kSigUR = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegGeneral, 2) | seg_sig_of(2, kSegIdentity, 5) | seg_sig_of(3, kSegRzP, 1) |
+                          seg_sig_of(4, kSegPermA, 4) | seg_sig_of(5, kSegPermB, 4) | seg_sig_of(6, kSegGeneral, 4);
 template <SegSig SIG, int J, class CV>
 RTB_HD void pose_mul_seg_by_sig(Pose &P, const CV &cv) { pose_mul_seg_sig<seg_sig_cls(SIG, J), seg_sig_tm(SIG, J)>(P, cv, J); }
 #ifndef RTB_SIG_KEEP_PINS
@@ -68,14 +77,7 @@ RTB_HD void pose_mul_seg_by_sig(Pose &P, const CV &cv) { pose_mul_seg_sig<seg_si
 #ifndef RTB_PIN_SEG_LOADS
 #define RTB_PIN_SEG_LOADS 1
 #endif
-// a chain view may carry a pointer to the sincos constants (k_ik: see sincos_reduced_tab in trig.h); the others use the literals
-template <class CV, class = void> struct cv_has_trig { static constexpr bool value = false; };
-template <class CV> struct cv_has_trig<CV, decltype((void)(((const CV *)nullptr)->trig))> { static constexpr bool value = true; };
-// ... or ask for the fused-chain translation  t += R c  (pose_t3_fma: the form every structured segment product is an instance of) without carrying the
-// sincos table: k_kin_diff's views (diff_kernel.h), so that its structure instantiations return its general kernel's bits
-template <class CV, class = void> struct cv_t3fma { static constexpr bool value = false; };
-template <class CV> struct cv_t3fma<CV, typename CV::t3fma_tag> { static constexpr bool value = true; };
-
+// (cv_has_trig / cv_t3fma, the chain views' traits: kin_device.h)
 // joint J of the walk (compile-time index: a signature picks the segment's form by it)
 template <int NJ, bool WANT_J, bool PLAIN, SegSig SIG, int J, class CV>
 RTB_HD void reg_walk_step(const CV &cv, Pose &P, double (&jac)[6 * NJ], const int (&jmv)[NJ], const double (&c)[NJ], const double (&s)[NJ], const double (&d)[NJ])
@@ -208,12 +210,25 @@ RTB_HD void reg_compute(const KinParams &kp, const CV &cv, const S *__restrict__
                         Pose &P, double (&jac)[6 * NJ])
 {
     const bool live = cfg < kp.N;
-    const S *qrow = q + cfg * kp.qw;
     double qv[NJ];
+    if constexpr (SIG != 0) {
+        // the launch's ramp is this kernel's to shorten: the NJ column words first, then NJ loads with nothing between them -- a dead lane reads
+        // row 0 (N >= 1) instead of branching round its load, which put a scalar load, its wait and a branch in front of every q load
+        const S *qrow = q + (live ? cfg : 0) * kp.qw;
+        int jq[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) qv[j] = live ? qrow[jm_jq(cv.jmeta[j])] : 0.0;
-    if constexpr (SIG != 0) reg_core<NJ, WANT_J, true, SIG>(cv, &cv.seg[NJ].r[0], kp.frame, qv, P, jac);
-    else reg_core<NJ, WANT_J>(cv, kp.tail, kp.frame, qv, P, jac);
+        for (int j = 0; j < NJ; ++j) jq[j] = jm_jq(cv.jmeta[j]);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) qv[j] = qrow[jq[j]];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) qv[j] = live ? qv[j] : 0.0;
+        reg_core<NJ, WANT_J, true, SIG>(cv, &cv.seg[NJ].r[0], kp.frame, qv, P, jac);
+    } else {
+        const S *qrow = q + cfg * kp.qw;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) qv[j] = live ? qrow[jm_jq(cv.jmeta[j])] : 0.0;
+        reg_core<NJ, WANT_J>(cv, kp.tail, kp.frame, qv, P, jac);
+    }
 }
 
 // staging: lane writes its finished J row / its 4x4 into the wave's LDS transposer
