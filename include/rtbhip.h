@@ -439,7 +439,10 @@ int rtbhip_device_identity(int32_t device, char *pci_bus_id32, unsigned char *uu
 int rtbhip_last_launch(int32_t *grid, int32_t *block, int32_t *lds_bytes);
 
 /* Tuning knobs for benchmarking (A/B of launch geometry / store paths); process-wide; unknown keys are ignored.  Results never
- * depend on them (every setting is covered by bit-equality tests); the defaults are the measured best.  IK scheduler:
+ * depend on them; the defaults are the measured best.  Bit-equality tests cover the keys that choose between kernel forms or schedules:
+ * "coalesced", "reg", "ik_flat", "ik_flat_l0", "ik_flat_len", "ik_share", "ik_donate_after", "ik_phased", "ik_plain", "ik_unit_we", "ik_sig",
+ * "kin_sig", "rne_sig", "tree_sig", "diff_sig", "sig_builtin", "jit", "host_chunk_kb", "shard_p2p", "rne_wpb".  The rest are geometry knobs (tiles per
+ * wave, waves per CU, scheduler pacing, which store path or launch shape a call takes) and have no test of their own.  IK scheduler:
  *   "ik_flat" 0 | 1 | 2       flat schedule (search ranges cut into chunks, (target, chunk) items drawn from one counter by whichever wave has
  *                             idle lanes): never / when the batch is resident at once (default) / always; "ik_flat_l0", "ik_flat_len": searches
  *                             in a target's first / in every later chunk (4, 8)
@@ -455,7 +458,8 @@ int rtbhip_last_launch(int32_t *grid, int32_t *block, int32_t *lds_bytes);
  * Others: "coalesced", "reg", "tiles_per_wave", "hess_mode" (fkine / Jacobian / Hessian store paths), "rne_tiles_per_wave",
  *         "partial3" 1 | 0 (order-3 partial_fkine0 on workgroups that own whole configurations / on the general kernel),
  *         "partial3_fused" 1 | 0 (that kernel forms the Hessians from the Jacobians it stages / reads a Hessian tensor written by a launch of its own),
- *         "rne_persist", "rne_wpb", "ik_unit_we" (A/B forms that measured slower and are off),
+ *         "ik_unit_we" 1 | 0 (a mask of ones takes the LM step without the weight products / the weighted step: the same bits),
+         "rne_wpb" 1 | 2 | 4 (waves per workgroup of k_rne, 7-joint modified-DH chains: an A/B form that measured slower and is off),
  *         "host_chunk_kb" (host-pointer pipeline), "shard_p2p" 1 | 0 (rtbhip_shard_gather: the grouped send / receive form for equal shards too). */
 /* Measurement aid, no reference counterpart: one launch of a plain streaming kernel that reads `read_doubles` doubles from `src` and writes
  * `write_doubles` doubles to `dst` (device pointers, 4 KiB-aligned; whole 4 KiB pages are moved, the tails are left alone) -- the memory rate this GPU delivers for a given read / write mix, which

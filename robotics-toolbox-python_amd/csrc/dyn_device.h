@@ -40,9 +40,6 @@ RTB_HD double dyn_pick(const double (&a)[NJ], int i)
     return r;
 }
 
-#ifndef RTB_DYN_BILINEAR
-#define RTB_DYN_BILINEAR 1      // 0: Dynamics.coriolis by the polar form over full passes (two per column) -- the first implementation, A/B
-#endif
 // ---- one column of C(q, qd), evaluated directly.  A Newton-Euler pass with gravity, friction and acceleration removed (what
 // Dynamics.coriolis runs, robot/Dynamics.py:811-861) is a quadratic form tau(v) = B(v, v) of the joint velocities, and the matrix the reference
 // assembles from its n + n (n - 1) / 2 unit-velocity passes is  C[:, k] = B(qd, e_k) = sum_j qd_j B(e_j, e_k).  B(u, w) comes out of ONE
@@ -258,102 +255,19 @@ RTB_HD void dyn_lane(LinksP links, const double *mine, double *mA, V3 grav, cons
         for (int j = 0; j < NJ; ++j) mA[j] = x[j];        // the tile's first n slots become the output row
     }
     if (MODE == kDynCoriolis) {
-        // What ships is rne_bilinear_core above (RTB_DYN_BILINEAR = 1): one two-field pass per column.  The rest of this comment describes the
-        // first implementation, kept under RTB_DYN_BILINEAR = 0 as the A/B baseline (scripts/build_variant.sh dyn_kernels dyn_polar ...):
-        // Dynamics.coriolis (robot/Dynamics.py:811-861) builds C from n passes at QD = e_i (Csq) and n (n - 1) / 2 passes at
-        // QD = e_i + e_j (gravity, friction and acceleration removed).  Such a pass is a homogeneous quadratic form of qd,
-        //      tau_r(v) = sum_ab h_rab v_a v_b   (h symmetric in a, b),
-        // the reference's combination (T_jk - Csq_j - Csq_k) / 2 is h_rjk, and its result is  C[r, k] = sum_j h_rjk qd_j  -- the
-        // polar form of tau against e_k.  The same numbers come from TWO passes per column instead of the reference's 28 in all:
-        //      C[:, k] = ( tau(qd + s e_k) - tau(qd - s e_k) ) / (4 s)          (exact for a quadratic form)
-        // with s the power of two next above max|qd_j| (1 for qd = 0), so that the probe is neither lost in qd nor qd in the probe,
-        // whatever the overall scale of the velocities, and the scaling is exact: 14 passes for a 7-joint arm; agreement with
-        // the reference's order of operations ~1e-15 of max|C| (tests: oracle.coriolis_dh statement for statement, emu and
-        // GPU, velocities from 1e-9 to 1e9).  Its rounding error scales with (max|qd|)^2 max|h| / s, the reference's with the
-        // largest single term |h_rjk qd_j|: for a row whose nonzero velocities span more than 2^16 the two can differ by that
-        // ratio, so such rows take the reference's own scheme below instead -- each row on its own (a wave that holds such a row, ~1 % of
-        // the waves with normally distributed velocities, runs both bodies under the execution mask), so that a row's result never depends
-        // on which other rows share its tile.
+        // One two-field pass per column (rne_bilinear_core above).  (The first implementation -- the polar form (tau(qd + s e_k) - tau(qd - s e_k)) / 4s,
+        // two full passes per column, with the reference's own n + n (n - 1) / 2 passes for rows whose velocities span more than 2^16 -- was
+        // replaced by it: profiles/retired_switches.md)
         // qd in registers: the kernel may keep the input row in the C tile itself, which the first pass starts to overwrite
-        double qdv[NJ], vmax = 0.0;
+        double qdv[NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) { qdv[j] = mine[NJ + j]; vmax = fmax(vmax, fabs(qdv[j])); }
-#if RTB_DYN_BILINEAR
-        // (what ships: the two-field pass above, one per column; the polar form below is kept as the A/B baseline)
-        (void)vmax;
+        for (int j = 0; j < NJ; ++j) qdv[j] = mine[NJ + j];
 #pragma unroll 1
         for (int k = 0; k < NJ; ++k) {
             dyn_opaque<NJ>(st, ct);
             rne_bilinear_core<NJ, MDH, ALLREV, SIG>(links, st, ct, qin, [&](int j) { return qdv[j]; }, k,
                                                [&](int r, double v) { mA[r * NJ + k] = 0.5 * v; }, k);
         }
-#else
-        // s = 2^ceil(log2(vmax)) through the exponent field (exact); 1 for qd = 0 and for non-finite rows (which come out NaN as
-        // they should); the exponent is kept where s^2 neither overflows nor underflows
-        int ex = 0;
-        const double mant = frexp(vmax, &ex);                      // vmax = mant 2^ex, mant in [0.5, 1)
-        if (mant == 0.5) ex -= 1;
-        if (!(vmax > 0.0) || !(vmax < 1.7e308)) ex = 0;
-        ex = ex > 400 ? 400 : (ex < -400 ? -400 : ex);
-        const double sc = ldexp(1.0, ex);
-        // (a row at rest is exactly zero, as in the reference -- not the rounding difference of the two probes)
-        const double inv4s = vmax > 0.0 || vmax != vmax ? 0.25 / sc : 0.0;
-        bool wide = false;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) wide = wide || (qdv[j] != 0.0 && fabs(qdv[j]) * 65536.0 < vmax);
-        auto polar = [&]() {
-#pragma unroll 1
-        for (int k = 0; k < NJ; ++k) {
-            dyn_opaque<NJ>(st, ct);
-            rne_core<NJ, MDH, false, ALLREV, true, false, false>(links, NJ, st, ct, zero, zero, zero, qin, [&](int j) { return j == k ? qdv[j] + sc : qdv[j]; },
-                                     [&](int) { return 0.0; }, [&](int r, double v) { mA[r * NJ + k] = v; });
-            dyn_opaque<NJ>(st, ct);
-            rne_core<NJ, MDH, false, ALLREV, true, false, false>(links, NJ, st, ct, zero, zero, zero, qin, [&](int j) { return j == k ? qdv[j] - sc : qdv[j]; },
-                                     [&](int) { return 0.0; }, [&](int r, double v) { mA[r * NJ + k] = (mA[r * NJ + k] - v) * inv4s; });
-        }
-        };
-        auto reference_scheme = [&]() {
-        // Dynamics.py:828-856 regrouped so that ONE n x n tile per lane suffices (the reference keeps Csq and C):
-        //   C[:,k] = sum_{j != k} (T_jk - Csq_k - Csq_j) qd_j / 2 + Csq_k qd_k
-        //          = 1/2 sum_{j != k} T_jk qd_j + Csq_k (2 qd_k - S / 2) - U / 2,   S = sum_j qd_j,  U = sum_j Csq_j qd_j
-        // with T_jk the pass at QD = e_j + e_k and Csq_j the pass at QD = e_j (friction removed, :820).  Same terms,
-        // different association: agreement with the reference order is ~1e-15 relative.
-        double S = 0.0, U[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) { S += qdv[j]; U[j] = 0.0; }
-#pragma unroll 1
-        for (int i = 0; i < NJ; ++i) {
-            const double qdi = dyn_pick<NJ>(qdv, i), wi = 2.0 * qdi - 0.5 * S;
-            dyn_opaque<NJ>(st, ct);
-            rne_core<NJ, MDH, false, ALLREV, true, false, false>(links, NJ, st, ct, zero, zero, zero, qin, [&](int j) { return j == i ? 1.0 : 0.0; },
-                                     [&](int) { return 0.0; }, [&](int r, double v) { mA[r * NJ + i] = v * wi; U[r] += v * qdi; });
-        }
-#pragma unroll
-        for (int r = 0; r < NJ; ++r)
-#pragma unroll
-            for (int c = 0; c < NJ; ++c) mA[r * NJ + c] -= 0.5 * U[r];
-#pragma unroll 1
-        for (int i = 0; i < NJ; ++i) {
-#pragma unroll 1
-            for (int j = i + 1; j < NJ; ++j) {
-                const double hi = 0.5 * dyn_pick<NJ>(qdv, i), hj = 0.5 * dyn_pick<NJ>(qdv, j);
-                dyn_opaque<NJ>(st, ct);
-                rne_core<NJ, MDH, false, ALLREV, true, false, false>(links, NJ, st, ct, zero, zero, zero, qin,
-                                         [&](int k) { return (k == i || k == j) ? 1.0 : 0.0; }, [&](int) { return 0.0; },
-                                         [&](int r, double tau) {
-                                             mA[r * NJ + j] += tau * hi;
-                                             mA[r * NJ + i] += tau * hj;
-                                         });
-            }
-        }
-        };
-        // the common case (no such row in the wave) is one straight wave-uniform body; only a wave that holds a wide row runs the per-lane choice.
-        // Price of the per-row choice against round 2's per-wave one, same box (visit z): 0.56 -> 0.60 ms per 1e6 (the form that runs the polar
-        // body for every lane and lets wide rows redo their tile measured the same)
-        if (!wave_any(wide)) polar();
-        else if (!wide) polar();
-        else reference_scheme();
-#endif
     }
 }
 

@@ -22,22 +22,8 @@
 #include "ldl.h"
 #include "diff_device.h"
 
-// Two compile-time A/B switches, measured against each other on one box in the steady state (round 4 visit h, scripts/gpu_r4_h.sh: four builds,
-// three interleaved rounds; (success, iterations, searches) of all 1e5 / 1e6 targets identical in every build):
-//                              config 3 (1e5)          notebook setting       1e6 targets
-//   neither                    1.105 1.098 1.102 ms    0.380 0.381 0.382      6.13 6.10 6.17
-//   RTB_IK_FAST_RCP only       1.082 1.085 1.082       0.375 0.374 0.375      6.02 6.00 6.08       <- shipped (-1.7 %)
-//   RTB_IK_FMOD_FMA only       1.120 1.117 1.112       0.382 0.382 0.381      6.25 6.09 6.20       (+1.3 %: fewer instructions per wrap, but the
-//   both                       1.102 1.099 1.099       0.376 0.374 0.375      6.12 6.22 6.19        extra branch lengthens the scheduling pass)
-#ifndef RTB_IK_FAST_RCP
-#define RTB_IK_FAST_RCP 1       // the LM step's seven pivot reciprocals through rcp_pivot (ldl.h): ~60 VALU instructions of 1633 per iteration
-#endif
-#ifndef RTB_IK_FMOD_FMA
-#define RTB_IK_FMOD_FMA 0       // 1: the end-of-search wrap through an exact FMA remainder instead of the library fmod (ik_fmod_2pi, below)
-#endif
-#ifndef RTB_IK_UNITW
-#define RTB_IK_UNITW 0          // 1: a second, multiplication-free copy of the LM step for a mask of ones.  Measured (round 3, visit y, four builds on
-#endif                          // one box): the copy costs 30 VGPRs (223 -> 256 + scratch) and 4-8 % of every IK line; the 48 products it saves do not pay
+// The LM step's seven pivot reciprocals go through rcp_pivot (ldl.h: ldl_solve<N, true>), ~60 VALU instructions of 1633 per iteration: -1.7 % on
+// config 3 (round 4 visit h, four builds, three interleaved rounds: 1.10 -> 1.08 ms, identical outcomes).  profiles/retired_switches.md
 
 namespace rtbhip {
 
@@ -137,41 +123,8 @@ RTB_HD double ik_half_weighted_square(const double (&e)[6], W we)
 
 // ---------------------------------------------------------------- one LM step
 // dq = (J^T W J + wn I)^-1 J^T W e, J in registers (slot r*NJ + j), W = diag(we).
-// The same step through the 6 x 6 system (unit weights, more joints than task dimensions):  (J^T J + wn 1)^-1 J^T e  =  J^T (J J^T + wn 1)^-1 e
-// for wn > 0 (push-through identity).  For the 7-joint arm: 21 entries of 7 products instead of 28 of 6, a 6 x 6 factorisation instead of a
-// 7 x 7 one -- 66 instructions fewer.  wn == 0 (a caller's k = 0) keeps the n x n form: there the reference inverts a singular matrix and the
-// two forms would disagree about the garbage.  MEASURED SLOWER and therefore off (round 4 visit o, one box, three interleaved rounds, sustained:
-// config 3 0.961 -> 1.004 ms, 1e6 targets 5.22 -> 5.52 ms): fewer instructions, but J must stay alive through the 6 x 6 solve for the final
-// J^T y, and the solve is one long dependent chain where the n x n form's right-hand side is formed alongside the matrix.  Kept as an A/B switch.
-#ifndef RTB_IK_DUAL
-#define RTB_IK_DUAL 0
-#endif
-template <int NJ>
-RTB_HD void ik_lm_step_dual(const double (&jac)[6 * NJ], const double (&e)[6], double wn, double (&dq)[NJ])
-{
-    double B[6][6], y[6], g[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        g[r] = e[r];
-#pragma unroll
-        for (int c = 0; c <= r; ++c) {
-            double a = 0.0;
-#pragma unroll
-            for (int k = 0; k < NJ; ++k) a += jac[r * NJ + k] * jac[c * NJ + k];
-            B[r][c] = (r == c) ? a + wn : a;
-        }
-    }
-    ldl_solve<6, RTB_IK_FAST_RCP != 0>(B, g, y);
-    sched_fence();
-#pragma unroll
-    for (int k = 0; k < NJ; ++k) {
-        double a = 0.0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r) a += jac[r * NJ + k] * y[r];
-        dq[k] = a;
-    }
-}
-
+// (The same step through the 6 x 6 system J^T (J J^T + wn 1)^-1 e -- 66 instructions fewer for the 7-joint arm -- MEASURED SLOWER, round 4 visit o:
+// config 3 0.961 -> 1.004 ms; J must stay alive through one long dependent solve.  profiles/retired_switches.md)
 template <int NJ, bool UNITW = false, class W>
 RTB_HD void ik_lm_step(const double (&jac)[6 * NJ], const double (&e)[6], W we /* we[k], k < 6 */, double wn,
                        double (&dq)[NJ])
@@ -202,7 +155,7 @@ RTB_HD void ik_lm_step(const double (&jac)[6 * NJ], const double (&e)[6], W we /
         }
     }
     sched_fence();   // J is dead from here on: do not let the factorisation overlap the products above
-    ldl_solve<NJ, RTB_IK_FAST_RCP != 0>(A, g, dq);
+    ldl_solve<NJ, true>(A, g, dq);
 }
 
 // ---------------------------------------------------------------- Gauss-Newton / Newton-Raphson steps
@@ -478,24 +431,9 @@ RTB_HD void ik_search_begin(IkLane<NJ> &st, QA qa, const PD &p, QL qlim, int64_t
     st.status = kIkRun;
 }
 
-// fmod(x, 2 pi) for the wrap at the end of a search, EXACT like the library's: with c = fl(2 pi) and n = the integer nearest to x / c, the
-// remainder r = x - n c is a multiple of 2^-50 of magnitude < 4 and therefore a double, so ONE fused multiply-add returns it without error
-// (an n that lands on the wrong side of a tie still gives |r| <= c / 2); fmod's result -- the remainder with the sign of x -- is r or r +- c,
-// again exact because fmod's own result is representable.  ~10 instructions against the library routine's ~35 (a bit-serial reduction loop);
-// seven of them per scheduling pass.  Beyond |x| = 2^40 (a diverged search) or for a non-finite x the library routine decides.
-RTB_HD double ik_fmod_2pi(double x)
-{
-#if RTB_IK_FMOD_FMA
-    if (fabs(x) < 1099511627776.0) {
-        const double n = rint(x * 0.15915494309189535);        // fl(1 / (2 pi))
-        double r = fma(-n, kIkPi2, x);
-        if (x >= 0.0) { if (r < 0.0) r += kIkPi2; }
-        else if (r > 0.0) r -= kIkPi2;
-        return r;
-    }
-#endif
-    return fmod(x, kIkPi2);
-}
+// fmod(x, 2 pi) for the wrap at the end of a search: the library routine.  (An exact one-FMA remainder, ~10 instructions against ~35, measured
+// +1.3 %: its extra branch lengthens the scheduling pass -- round 4 visit h, again round 5.  profiles/retired_switches.md)
+RTB_HD double ik_fmod_2pi(double x) { return fmod(x, kIkPi2); }
 RTB_HD double ik_wrap_c(double q) { return ik_fmod_2pi(q + kIkPi) - kIkPi; }        // ik.cpp:51
 RTB_HD double ik_wrap_py(double q)                                                      // IK.py:331 (2 * fl(pi) == fl(2 pi): the same modulus)
 {
@@ -573,11 +511,7 @@ RTB_HD void ik_iter(IkLane<NJ> &st, const PD &p, const CV &cv, QL qlim, TD td, Q
         if (!qp_done) ik_pinv_step<NJ>(jac, e, rows, d2, &p.we[0], p.method == 3, dq);
     } else {
         const double wn = (p.method == 1) ? p.lambda : (p.method == 2) ? E + p.lambda : p.lambda * E;   // ik.cpp:169,183,205
-        if constexpr (UNITW && RTB_IK_DUAL && NJ >= 7) {
-            if (p.lambda > 0.0 || p.method == 2) ik_lm_step_dual<NJ>(jac, e, wn, dq);      // wave-uniform; (sugihara: wn = E + lambda > 0 off the solution)
-            else ik_lm_step<NJ, true>(jac, e, &p.we[0], wn, dq);
-        } else if constexpr (UNITW) ik_lm_step<NJ, true>(jac, e, &p.we[0], wn, dq);
-        else if (RTB_IK_UNITW && p.unit_we) ik_lm_step<NJ, true>(jac, e, &p.we[0], wn, dq);          // wave-uniform
+        if constexpr (UNITW) ik_lm_step<NJ, true>(jac, e, &p.we[0], wn, dq);
         else ik_lm_step<NJ, false>(jac, e, &p.we[0], wn, dq);
     }
     if constexpr (NULLSP) {
@@ -701,21 +635,10 @@ RTB_HD void ik_emit(const IkLane<NJ> &st, QA qa, const PD &p, QL qlim, int64_t t
 #define RTB_IK_RING 64
 #endif
 constexpr int kIkRing = RTB_IK_RING;        // outstanding (unaccounted) searches per slot (a power of two)
-// A/B knobs of the three-waves-per-SIMD study (profiles/r06_ik_three_waves.txt; scripts/build_ik_variant.sh): twelve waves on a CU leave each
-// 13 653 B of LDS -- RTB_IK_REC8 packs a search record into 8 bits (iterations <= 62: the launcher refuses a larger ilimit in such a build),
-// RTB_IK_QROWS_EXACT sizes the q rows to the kernel's joint count instead of its class (7 rows for the Panda, not 8); with a ring of 32
-// that is 13 624 B for a 7-joint arm.  The product keeps 16-bit records, a ring of 64, 8 rows: 20 280 B, eight waves.
-#ifndef RTB_IK_REC8
-#define RTB_IK_REC8 0
-#endif
-#ifndef RTB_IK_QROWS_EXACT
-#define RTB_IK_QROWS_EXACT 0
-#endif
-#if RTB_IK_REC8
-typedef uint8_t IkRec;
-#else
+// 16-bit records, a ring of 64, 8 q rows: 20 280 B, eight waves per CU.  (The three-waves-per-SIMD study, profiles/r06_ik_three_waves.txt, tried 8-bit
+// records, q rows sized to the joint count and a ring of 32 -- 13 624 B for a 7-joint arm, twelve waves -- and did not keep them:
+// profiles/retired_switches.md)
 typedef uint16_t IkRec;
-#endif
 template <int QR>
 struct alignas(16) IkWaveSharedT {
     uint32_t vix[64];                       // work-item index = output row (the target itself without a work list; < 2^32)
@@ -733,7 +656,7 @@ struct alignas(16) IkWaveSharedT {
     double q[QR][64];                       // per LANE: the joint vector of that search
 };
 // q rows by joint-count class: 8 (the register-resident kernels), 16 (the other built-in sizes), RTBHIP_MAX_JOINTS (sizes instantiated at run time)
-template <int NJ> using IkWaveSharedFor = IkWaveSharedT<(RTB_IK_QROWS_EXACT ? NJ : (NJ <= kRegMaxJoints ? kRegMaxJoints : (NJ <= kIkMaxJoints ? kIkMaxJoints : RTBHIP_MAX_JOINTS)))>;
+template <int NJ> using IkWaveSharedFor = IkWaveSharedT<(NJ <= kRegMaxJoints ? kRegMaxJoints : (NJ <= kIkMaxJoints ? kIkMaxJoints : RTBHIP_MAX_JOINTS))>;
 static_assert(sizeof(IkWaveSharedT<kRegMaxJoints>) * 8 <= 160 * 1024, "8 IK waves per CU must fit the LDS");
 
 // A work item: searches s0 .. s1 (inclusive, in the flavour's own numbering) of target `tgt`.  Without a work list item v is
@@ -744,7 +667,7 @@ struct IkWork { int32_t tgt; int16_t s0, s1; };
 RTB_HD unsigned long long ik_pack(IkWork w) { return (unsigned long long)(uint32_t)w.tgt | ((unsigned long long)(uint16_t)w.s0 << 32) | ((unsigned long long)(uint16_t)w.s1 << 48); }
 RTB_HD IkWork ik_unpack(unsigned long long x) { IkWork w; w.tgt = (int32_t)(uint32_t)x; w.s0 = (int16_t)(x >> 32); w.s1 = (int16_t)(x >> 48); return w; }
 constexpr int kIkMaxSlimit = 32000;
-constexpr int kIkMaxIlimit = RTB_IK_REC8 ? 62 : 16000;         // (ilimit + 1) << 2 must fit the record
+constexpr int kIkMaxIlimit = 16000;         // (ilimit + 1) << 2 must fit the record
 
 template <class SH>
 struct IkLdsQT {   // accessor of one lane's q column in the wave's LDS

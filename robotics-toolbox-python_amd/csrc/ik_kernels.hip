@@ -59,34 +59,12 @@ constexpr int kIkNullMax = 12;   // null-space step variants: 6..8 joints in reg
 #ifndef RTB_IK_WAVES
 #define RTB_IK_WAVES 2
 #endif
-#ifndef RTB_IK_PASS_LOW
-#define RTB_IK_PASS_LOW -1      // >= 0: a wave with at most this many running lanes passes at every iteration in which a search has ended (A/B, round 5)
-#endif
-#ifndef RTB_IK_SHARE
-#define RTB_IK_SHARE 1          // 0: build without the cross-wave sharing code (A/B of what its presence costs the plain schedule)
-#endif
 // AUX: bit 0 = the flat schedule, bit 1 = the per-wave diagnostic counters (RTBHIP_IK_STATS).  Compile-time, because carrying either through the
 // persistent loop as run-time switches cost the plain schedule 6-9 % (20 VGPRs; round 3, visit x: the round-2 build against this one on one box).
 constexpr int kIkStatWords = 6;  // per wave: loop iterations, scheduling passes, lane-iterations on a running search, items started, shader cycles, 100 MHz ticks
 constexpr int kIkAuxFlat = 1, kIkAuxStats = 2, kIkAuxUnitW = 4;      // bit 2: every mask weight is 1 (the default), LM steps: ik_iter<..., UNITW>
-#ifndef RTB_IK_MASK_IDLE
-#define RTB_IK_MASK_IDLE 0
-#endif
 constexpr int kIkAuxPlain = 8;                                         // bit 3: all-revolute chain, no flipped joint: ik_iter<..., PLAIN>
-// Structure signatures this build has straight-line instantiations for (kin_reg.h: SegSig; the chain compiler's classes, rtbhip_internal.h).  A
-// signature is a property of the robot's constants; the launcher compares a chain's own with this list and falls back to the general kernels.
-//   Franka Panda as the reference models it (models/ETS/Panda.py:32-54), BASELINE config 3's arm: C_0 = tz, C_1 .. C_6 quarter turns about x with
-//   translations on some axes, the flange Rz(-pi/4) tz(0.103) as the tail.
-constexpr SegSig kIkSigPandaETS = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegRxN, 0) | seg_sig_of(2, kSegRxP, 6) | seg_sig_of(3, kSegRxP, 1) |
-                                  seg_sig_of(4, kSegRxN, 7) | seg_sig_of(5, kSegRxP, 0) | seg_sig_of(6, kSegRxP, 7) | seg_sig_of(7, kSegRz, 4);
-//   The same arm read from its URDF (rtb-data franka_description, to the default end effector): the constants' tiny cos(pi/2) terms fall on other entries.
-constexpr SegSig kIkSigPandaURDF = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegRxN, 0) | seg_sig_of(2, kSegRxP, 2) | seg_sig_of(3, kSegRxP, 1) |
-                                   seg_sig_of(4, kSegRxN, 3) | seg_sig_of(5, kSegRxP, 0) | seg_sig_of(6, kSegRxP, 1) | seg_sig_of(7, kSegRz, 4);
-//   Universal Robots UR3 / UR5 / UR10 from their URDFs (ur_description, to tool0): six joints, one signature for the three sizes.
-constexpr SegSig kIkSigUR = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegGeneral, 2) | seg_sig_of(2, kSegIdentity, 5) | seg_sig_of(3, kSegRzP, 1) |
-                            seg_sig_of(4, kSegPermA, 4) | seg_sig_of(5, kSegPermB, 4) | seg_sig_of(6, kSegGeneral, 4);
-// (k_kin_reg is instantiated for the same three: kin_reg.h holds them as kSig*, one definition for both files to agree with)
-static_assert(kIkSigPandaETS == kSigPandaETS && kIkSigPandaURDF == kSigPandaURDF && kIkSigUR == kSigUR, "the built-in signatures of k_ik and k_kin_reg are the same robots");
+// (the structure signatures this build has straight-line instantiations for: kin_reg.h, kSig*)
 static int g_ik_sig = 1;          // rtbhip_tune("ik_sig", 0): never take a signature's instantiation (A/B, tests)
 template <int NJ, int STEP, int AUX = 0, SegSig SIG = 0>
 __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints && !(STEP & kIkStepNull) ? RTB_IK_WAVES : 1)) void k_ik(IkDev p, DevChain dc, const double *qlim_g, const double *__restrict__ Tep,
@@ -141,20 +119,15 @@ __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints && !(STEP & kIkStepNull
     int leave = 0;                    // set by a pass: 1 the wave is done, 2 out of work with sharing on (take a ticket and wait)
     const long long patience = ik_patience(p, s_last);    // watchdog budget (ik_device.h), the pass latency included
     long long quiet = 0;
-    const bool sharing = RTB_IK_SHARE && share_g.tc != nullptr;   // wave-uniform
+    const bool sharing = share_g.tc != nullptr;   // wave-uniform
     for (;;) {
         asm volatile("" : "+s"(ka));
         // the scheduling pass runs when some search has ended -- at most every (pass_mask + 1)-th iteration: a
         // finished lane then idles for up to pass_mask iterations (of ~31 per search) and the pass, several
         // hundred mostly scalar / LDS instructions, is amortised over more useful iterations
-#if RTB_IK_PASS_LOW >= 0
-        // ... and at ANY iteration once at most RTB_IK_PASS_LOW lanes of the wave still run a search: the pass then costs less than the lanes it refills
-        // (0: only when nothing runs at all -- the iterations a wave would otherwise burn waiting for its pass slot)
-        const bool pass_slot = (tick++ & ka->p.pass_mask) == 0 || __popcll(__ballot(st.status == kIkRun && !st.fin)) <= RTB_IK_PASS_LOW;
-        if (first || (pass_slot && __any(st.fin != 0))) {
-#else
+        // (passing at ANY iteration once at most 0 / 8 / 16 / 32 lanes of the wave still run a search was A/B'd in round 5 and not kept:
+        // profiles/retired_switches.md)
         if (first || ((tick++ & ka->p.pass_mask) == 0 && __any(st.fin != 0))) {
-#endif
             first = false;
             if constexpr (kStats) ++st_passes;
             unsigned long long busy = ws_get64(ws.busy), pool_next = ws_get64(ws.pool_next), pool_end = ws_get64(ws.pool_end), pool_live = ws_get64(ws.pool_live);
@@ -440,12 +413,8 @@ __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints && !(STEP & kIkStepNull
             asm volatile("" : "+s"(cvi.seg), "+s"(cvi.jmeta), "+s"(ql), "+s"(cvi.trig));
             const int myslot = st.slot;
             if constexpr (kStats) { ++st_iters; st_lane += (unsigned long long)__popcll(__ballot(st.status == kIkRun && !st.fin)); }
-#if RTB_IK_MASK_IDLE
-            // lanes without a running search sit the iteration out with their EXEC bit cleared: the instruction stream is the same, but a
-            // third of the lane slots (idle and parked lanes, r04_g_ik_occupancy.txt) no longer toggle operands -- on a power-limited part
-            // that is clock (A/B: round 4 visit q)
-            if (st.status == kIkRun && !st.fin)
-#endif
+            // (lanes without a running search execute the iteration too; clearing their EXEC bit for it was A/B'd in round 4 visit q and not
+            // kept: profiles/retired_switches.md)
             ik_iter<NJ, STEP, (AUX & kIkAuxUnitW) != 0 && STEP == 0, (AUX & kIkAuxPlain) != 0, SIG>(st, ka->p, cvi, ql, [&](int k) { return sh.Td[k][myslot]; }, ik_lds_q(sh, lane));
         }
     }
@@ -602,8 +571,8 @@ void ik_restart_host(const Chain *c, uint64_t seed, int64_t target, int draw, do
     }
 }
 
-// Signatures with an instantiation built into the library (kIkSig*); every other plain chain of up to 8 joints gets its own at run time (jit.cpp).
-static bool ik_sig_builtin(int n, SegSig sig) { return jit_builtin_enabled() && ((n == 7 && (sig == kIkSigPandaETS || sig == kIkSigPandaURDF)) || (n == 6 && sig == kIkSigUR)); }
+// Signatures with an instantiation built into the library (kin_reg.h: kSig*); every other plain chain of up to 8 joints gets its own at run time (jit.cpp).
+static bool ik_sig_builtin(int n, SegSig sig) { return jit_builtin_enabled() && ((n == 7 && (sig == kSigPandaETS || sig == kSigPandaURDF)) || (n == 6 && sig == kSigUR)); }
 static std::string ik_jit_expr(int n, bool flat, SegSig sig)
 {
     return "rtbhip::k_ik<" + std::to_string(n) + ", 0, " + std::to_string((flat ? kIkAuxFlat : 0) | kIkAuxUnitW | kIkAuxPlain) + ", " + jit_hex(sig) + ">";
@@ -649,11 +618,11 @@ static void launch_nj(const Chain *c, dim3 grid, hipStream_t s, const IkDev &p, 
         return;                                                                                                                                         \
     }
                 if constexpr (NJ == 7) {
-                    RTB_IK_SIG_LAUNCH(kIkSigPandaETS)
-                    RTB_IK_SIG_LAUNCH(kIkSigPandaURDF)
+                    RTB_IK_SIG_LAUNCH(kSigPandaETS)
+                    RTB_IK_SIG_LAUNCH(kSigPandaURDF)
                 }
                 if constexpr (NJ == 6) {
-                    RTB_IK_SIG_LAUNCH(kIkSigUR)
+                    RTB_IK_SIG_LAUNCH(kSigUR)
                 }
 #undef RTB_IK_SIG_LAUNCH
                 // any other robot: its own instantiation of the same kernel, compiled at run time; the general walk below serves until it is there
@@ -677,9 +646,9 @@ static void launch_nj(const Chain *c, dim3 grid, hipStream_t s, const IkDev &p, 
     if constexpr (NJ == 7) {                              // the counters: the benchmark's arm only
         // ... on the very instantiation that serves config 3 (the Panda's signature, unit mask): lane utilisation and the effective clock on the bench line
         // (benchsecondary.py: ik_loss_factors) are then those of the kernel that is timed, not of the general one
-        if (stats && p.unit_we && p.pad_we && g_ik_plain && g_ik_sig && chain_sig == kIkSigPandaETS && ik_sig_builtin(NJ, chain_sig)) {
-            if (flat) hipLaunchKernelGGL((k_ik<NJ, 0, kIkAuxFlat | kIkAuxStats | kIkAuxUnitW | kIkAuxPlain, kIkSigPandaETS>), grid, dim3(kWave), 0, s, p, dc, qlim, Tep, q0, ctr, q_out, success, iters, searches, residual, work, count, share);
-            else hipLaunchKernelGGL((k_ik<NJ, 0, kIkAuxStats | kIkAuxUnitW | kIkAuxPlain, kIkSigPandaETS>), grid, dim3(kWave), 0, s, p, dc, qlim, Tep, q0, ctr, q_out, success, iters, searches, residual, work, count, share);
+        if (stats && p.unit_we && p.pad_we && g_ik_plain && g_ik_sig && chain_sig == kSigPandaETS && ik_sig_builtin(NJ, chain_sig)) {
+            if (flat) hipLaunchKernelGGL((k_ik<NJ, 0, kIkAuxFlat | kIkAuxStats | kIkAuxUnitW | kIkAuxPlain, kSigPandaETS>), grid, dim3(kWave), 0, s, p, dc, qlim, Tep, q0, ctr, q_out, success, iters, searches, residual, work, count, share);
+            else hipLaunchKernelGGL((k_ik<NJ, 0, kIkAuxStats | kIkAuxUnitW | kIkAuxPlain, kSigPandaETS>), grid, dim3(kWave), 0, s, p, dc, qlim, Tep, q0, ctr, q_out, success, iters, searches, residual, work, count, share);
             return;
         }
         if (stats && flat) { hipLaunchKernelGGL((k_ik<NJ, 0, kIkAuxFlat | kIkAuxStats>), grid, dim3(kWave), 0, s, p, dc, qlim, Tep, q0, ctr, q_out, success, iters, searches, residual, work, count, share); return; }

@@ -93,7 +93,7 @@ RTB_HD void pose_tx(Pose &P, double d) { P.tx = fmax_(d, P.r00, P.tx); P.ty = fm
 RTB_HD void pose_ty(Pose &P, double d) { P.tx = fmax_(d, P.r01, P.tx); P.ty = fmax_(d, P.r11, P.ty); P.tz = fmax_(d, P.r21, P.tz); }
 RTB_HD void pose_tz(Pose &P, double d) { P.tx = fmax_(d, P.r02, P.tx); P.ty = fmax_(d, P.r12, P.ty); P.tz = fmax_(d, P.r22, P.tz); }
 // P.t += R (x, y, z) as three fused chains seeded with the old translation (one instruction less per component than sum-then-add; used by
-// k_ik's plain walk, A/B switch RTB_POSE_T3_FMA)
+// k_ik's plain walk)
 RTB_HD void pose_t3_fma(Pose &P, double x, double y, double z)
 {
     P.tx = fmax_(z, P.r02, fmax_(y, P.r01, fmax_(x, P.r00, P.tx)));
@@ -225,7 +225,7 @@ RTB_HD void pose_mul_seg_sig(Pose &P, const CV &cv, int j)
 }
 // run-time class (a wave-uniform switch on the descriptor): measured SLOWER than the general product inside k_ik (round 5 visit c: config 3
 // 0.986 against 0.939 ms -- the ~45 scalar branches per iteration cost more than the ~170 vector operations they save); kept for the host
-// replay's tests and as an A/B switch (RTB_SEG_CLASSES = 1)
+// replay's tests (no kernel calls it)
 template <class CV>
 RTB_HD void pose_mul_seg_cls(Pose &P, const CV &cv, int j, int jm)
 {

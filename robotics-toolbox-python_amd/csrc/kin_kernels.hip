@@ -26,18 +26,13 @@ namespace rtbhip {
 // absorbed by that cache and rewritten in place (with three or more output sets used in rotation both forms take 90 us).  Beyond that size
 // ordinary stores lose (2e6 configurations: 188-200 us against 148-171), so the launcher turns them on (KinParams.pad bit 0) only for a
 // pose array of at most kPoseCacheBytes; everything else -- fkine alone, the fleet, long batches -- streams non-temporally as before.
-// RTB_T_PLAIN_MAX_BYTES = 0 restores the form of rounds 1-3 (A/B).
-#ifndef RTB_T_FIRST
-#define RTB_T_FIRST 1
-#endif
+// RTB_T_PLAIN_MAX_BYTES = 0 restores the form of rounds 1-3 (A/B).  (T after J, the order of rounds 1-3, was the other side of that measurement:
+// profiles/retired_switches.md)
 #ifndef RTB_T_PLAIN_MAX_BYTES
 #define RTB_T_PLAIN_MAX_BYTES (136ll << 20)
 #endif
 constexpr long long kPoseCacheBytes = RTB_T_PLAIN_MAX_BYTES;
 constexpr int kKinPosePlain = 1;      // KinParams.pad bit 0
-#ifndef RTB_PACKED_XCD
-#define RTB_PACKED_XCD 1
-#endif
 constexpr int kKinPacked = 2;         // KinParams.pad bit 1: T is the packed (N, 16 + 6n) array [T | J], J is not written separately (run-time-n tile)
 
 // the run-time-n tile loop; S = storage type of q, T and J (kin_tile.h: double, or float for the _f32 entry points; H is fp64 only)
@@ -144,7 +139,6 @@ __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &
         }
         return;
     }
-#if RTB_T_FIRST
     if (WANT_T) {
         reg_stage_T(kp, P, buf, lane);
         __syncthreads();
@@ -152,7 +146,6 @@ __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &
         else kin_flush<true>(buf, 17, 16, ncfg, T + cfg0 * 16, lane);
         __syncthreads();
     }
-#endif
     if (WANT_J) {
 #pragma unroll
         for (int r = 0; r < kWave / kJRound; ++r) {
@@ -164,14 +157,6 @@ __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &
             __syncthreads();
         }
     }
-#if !RTB_T_FIRST
-    if (WANT_T) {
-        reg_stage_T(kp, P, buf, lane);
-        __syncthreads();
-        if (kp.pad & kKinPosePlain) kin_flush<false>(buf, 17, 16, ncfg, T + cfg0 * 16, lane);
-        else kin_flush<true>(buf, 17, 16, ncfg, T + cfg0 * 16, lane);
-    }
-#endif
 }
 
 // ONE tile per single-wave workgroup, no grid-stride loop: with a loop LICM hoists every segment's
@@ -186,8 +171,8 @@ __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints ? RTB_REG_WAVES : 2)) v
                                                   double *__restrict__ T, double *__restrict__ J)
 {
     extern __shared__ __attribute__((aligned(16))) double buf[];
-    // (the packed form writes ~30 KB runs per wave: like the Hessian tile it may prefer the identity mapping -- RTB_PACKED_XCD, A/B'd in profiles/r05_*)
-    reg_tile<NJ, WANT_T, WANT_J, PACKED, SIG>(kp, const_view(dc), q, T, J, buf, threadIdx.x, (PACKED && !RTB_PACKED_XCD) ? blockIdx.x : xcd_tile());
+    // (the packed form writes ~30 KB runs per wave; the identity mapping the Hessian tile prefers was A/B'd for it in profiles/r05_* and not kept)
+    reg_tile<NJ, WANT_T, WANT_J, PACKED, SIG>(kp, const_view(dc), q, T, J, buf, threadIdx.x, xcd_tile());
 }
 // float32 q, T, J (PACKED: [T | J] rows): the same tile, the same launch shape; only the widths of the row accesses differ (kin_tile.h)
 template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false, SegSig SIG = 0>
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(kWave, (NJ <= kRegMaxJoints ? RTB_REG_WAVES : 2)) v
                                                       float *__restrict__ T, float *__restrict__ J)
 {
     extern __shared__ __attribute__((aligned(16))) double buf[];
-    reg_tile<NJ, WANT_T, WANT_J, PACKED, SIG>(kp, const_view(dc), q, T, J, buf, threadIdx.x, (PACKED && !RTB_PACKED_XCD) ? blockIdx.x : xcd_tile());
+    reg_tile<NJ, WANT_T, WANT_J, PACKED, SIG>(kp, const_view(dc), q, T, J, buf, threadIdx.x, xcd_tile());
 }
 
 static int g_hess_mode = 0;   // A/B knob (rtbhip_tune "hess_mode")
@@ -837,10 +822,7 @@ __global__ __launch_bounds__(kWave, (CLS == 0 ? RTB_REG_WAVES : 2)) void k_fleet
     // each call then rewrites the SAME 128 MB pose array, which the memory-side cache absorbs (store policy above); a fleet step writes 2 GB of poses
     // once: it streams, at 0.72-0.73 of the HBM roof against 0.745 for a plain fill of the same bytes: profiles/r05_r_fleet_probe.jsonl.)
     const int64_t local = gt - fe.tile0, ctiles = (fe.N + kWave - 1) / kWave;
-#ifndef RTB_FLEET_XCD
-#define RTB_FLEET_XCD 1
-#endif
-    const int64_t tile = (RTB_FLEET_XCD && ctiles <= 0x7fffffff) ? (int64_t)xcd_tile_of((unsigned)ctiles, (unsigned)local) : local;
+    const int64_t tile = (ctiles <= 0x7fffffff) ? (int64_t)xcd_tile_of((unsigned)ctiles, (unsigned)local) : local;
     if (CLS == 0) {
         switch (fe.n) {
         case 1: reg_tile<1, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;

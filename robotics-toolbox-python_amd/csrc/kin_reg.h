@@ -43,12 +43,8 @@ RTB_HD int reg_lds_doubles_packed(int n) { return kPRound * (17 + 6 * n + 1); }
 // Per-lane core: joint values qv[] (chain order, as the caller holds them) -> P = C_0 Z_0 ... tail and
 // the finished Jacobian in registers.  jac slot r*NJ + j : rows 0..2 = p_j, rows 3..5 = z_j until
 // the closing loop finishes them.  Used by the tile kernel (reg_compute) and by the IK loop.
-#ifndef RTB_POSE_T3_FMA
-#define RTB_POSE_T3_FMA 1
-#endif
-#ifndef RTB_SEG_CLASSES
-#define RTB_SEG_CLASSES 0      // 1: k_ik multiplies by a constant segment through a RUN-TIME switch on its structure class (kin_device.h: pose_mul_seg_cls).
-#endif                         //    Measured slower than the general product (round 5 visit c); what ships is the COMPILE-TIME form below.
+// (k_ik choosing a segment's product by a RUN-TIME switch on its structure class -- kin_device.h: pose_mul_seg_cls -- measured slower than the general
+// product, round 5 visit c; what ships is the COMPILE-TIME form below.  profiles/retired_switches.md)
 // A chain's STRUCTURE SIGNATURE: 7 bits per constant segment C_0 .. C_n (class | translation mask << 4, rtbhip_internal.h: kSeg*), bit 63 = "present".
 // reg_core<..., SIG != 0> multiplies by every segment through pose_mul_seg_sig<class, mask>: straight-line code, no descriptor is read.  A
 // kernel instantiated for a signature serves exactly the chains whose table has it (ik_kernels.hip: the launcher compares).
@@ -60,23 +56,20 @@ inline SegSig chain_signature(const int32_t *jmeta, int n)      // host: from th
     for (int j = 0; j <= n; ++j) s |= seg_sig_of(j, jm_cls(jmeta[j]), jm_tmask(jmeta[j]));
     return s;
 }
-// Structure signatures k_kin_reg has straight-line instantiations for (kin_kernels.hip) -- the robots of k_ik's built-in list (ik_kernels.hip: kIkSig*,
-// which says where each comes from and asserts that the two lists agree).  A signature is a property of the robot's constants; the launcher compares
-// a chain's own with this list and falls back to the general kernel.
+// The built-in structure signatures: k_kin_reg (kin_kernels.hip) and k_ik (ik_kernels.hip) have straight-line instantiations for each.  A signature is
+// a property of the robot's constants; the launchers compare a chain's own with this list and fall back to the general kernel.
+//   Franka Panda as the reference models it (models/ETS/Panda.py:32-54), BASELINE config 3's arm: C_0 = tz, C_1 .. C_6 quarter turns about x with
+//   translations on some axes, the flange Rz(-pi/4) tz(0.103) as the tail.
 constexpr SegSig kSigPandaETS = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegRxN, 0) | seg_sig_of(2, kSegRxP, 6) | seg_sig_of(3, kSegRxP, 1) |
                                 seg_sig_of(4, kSegRxN, 7) | seg_sig_of(5, kSegRxP, 0) | seg_sig_of(6, kSegRxP, 7) | seg_sig_of(7, kSegRz, 4);
+//   The same arm read from its URDF (rtb-data franka_description, to the default end effector): the constants' tiny cos(pi/2) terms fall on other entries.
 constexpr SegSig kSigPandaURDF = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegRxN, 0) | seg_sig_of(2, kSegRxP, 2) | seg_sig_of(3, kSegRxP, 1) |
                                  seg_sig_of(4, kSegRxN, 3) | seg_sig_of(5, kSegRxP, 0) | seg_sig_of(6, kSegRxP, 1) | seg_sig_of(7, kSegRz, 4);
+//   Universal Robots UR3 / UR5 / UR10 from their URDFs (ur_description, to tool0): six joints, one signature for the three sizes.
 constexpr SegSig kSigUR = kSegSigPresent | seg_sig_of(0, kSegIdentity, 4) | seg_sig_of(1, kSegGeneral, 2) | seg_sig_of(2, kSegIdentity, 5) | seg_sig_of(3, kSegRzP, 1) |
                           seg_sig_of(4, kSegPermA, 4) | seg_sig_of(5, kSegPermB, 4) | seg_sig_of(6, kSegGeneral, 4);
 template <SegSig SIG, int J, class CV>
 RTB_HD void pose_mul_seg_by_sig(Pose &P, const CV &cv) { pose_mul_seg_sig<seg_sig_cls(SIG, J), seg_sig_tm(SIG, J)>(P, cv, J); }
-#ifndef RTB_SIG_KEEP_PINS
-#define RTB_SIG_KEEP_PINS 0    // 1: signature kernels keep the load pins and every fence of the general plain walk (A/B)
-#endif
-#ifndef RTB_PIN_SEG_LOADS
-#define RTB_PIN_SEG_LOADS 1
-#endif
 // (cv_has_trig / cv_t3fma, the chain views' traits: kin_device.h)
 // joint J of the walk (compile-time index: a signature picks the segment's form by it)
 template <int NJ, bool WANT_J, bool PLAIN, SegSig SIG, int J, class CV>
@@ -84,23 +77,21 @@ RTB_HD void reg_walk_step(const CV &cv, Pose &P, double (&jac)[6 * NJ], const in
 {
     constexpr int j = J;
     {
-#if defined(__HIP_DEVICE_COMPILE__) && RTB_PIN_SEG_LOADS
+#if defined(__HIP_DEVICE_COMPILE__)
         // Inside k_ik's persistent loop (the chain views that carry `trig`): tie segment j's table pointer to a value of step j - 1, so that its
         // scalar loads cannot be issued before the walk gets there.  Without this the loads of the later segments were issued early and their
         // results parked in VGPR lanes (v_writelane) until needed (v_readlane): 475 -> 251 such instructions in the kernel, 253 -> 244 VGPRs,
-        // -2.4 % (config 3) ... -3.6 % (notebook setting) on one box (round 4 visit l).  RTB_PIN_SEG_LOADS = 2 pins the general (branchy) walk too.
+        // -2.4 % (config 3) ... -3.6 % (notebook setting) on one box (round 4 visit l).
         CV cvj = cv;
         // (a signature kernel reads two or three scalars per segment instead of twelve: there the pin and the fences only cost -- round 5
         // visits f, k, three interleaved rounds each: config 3 0.844 -> 0.833 -> 0.830 ms without them, outputs bit-identical)
-        if ((PLAIN || RTB_PIN_SEG_LOADS > 1) && (SIG == 0 || RTB_SIG_KEEP_PINS) && cv_has_trig<CV>::value && j > 0) asm volatile("" : "+s"(cvj.seg), "+v"(P.tx));
+        if (PLAIN && SIG == 0 && cv_has_trig<CV>::value && j > 0) asm volatile("" : "+s"(cvj.seg), "+v"(P.tx));
         if (j == 0) pose_from_seg(P, cvj, 0);
         else if constexpr (SIG != 0) pose_mul_seg_by_sig<SIG, J>(P, cvj);                                              // k_ik for a known robot: compile-time class
-        else if constexpr (RTB_SEG_CLASSES && cv_has_trig<CV>::value) pose_mul_seg_cls(P, cvj, j, cvj.jmeta[j]);      // k_ik: by structure class (run-time switch, A/B)
-        else pose_mul_seg<((PLAIN && RTB_POSE_T3_FMA && cv_has_trig<CV>::value) || cv_t3fma<CV>::value)>(P, cvj, j);
+        else pose_mul_seg<((PLAIN && cv_has_trig<CV>::value) || cv_t3fma<CV>::value)>(P, cvj, j);
 #else
         if (j == 0) pose_from_seg(P, cv, 0);
         else if constexpr (SIG != 0) pose_mul_seg_by_sig<SIG, J>(P, cv);
-        else if constexpr (RTB_SEG_CLASSES && cv_has_trig<CV>::value) pose_mul_seg_cls(P, cv, j, cv.jmeta[j]);          // (the host replay of k_ik: the same arithmetic)
         else pose_mul_seg<cv_t3fma<CV>::value>(P, cv, j);
 #endif
         if (WANT_J) {
@@ -110,11 +101,7 @@ RTB_HD void reg_walk_step(const CV &cv, Pose &P, double (&jac)[6 * NJ], const in
         // revolute: rotate by (c, s); prismatic: slide d -- a wave-uniform branch on the joint descriptor (s_cbranch)
         if (jm_prismatic(jmv[j])) pose_tz(P, d[j]);
         else pose_rotz(P, c[j], s[j]);
-#if defined(RTB_PLAIN_FENCE_EVERY)
-        if (!PLAIN || (j % RTB_PLAIN_FENCE_EVERY) == RTB_PLAIN_FENCE_EVERY - 1) sched_fence();      // A/B: fewer fences in the straight-line walk
-#else
-        if (SIG == 0 || RTB_SIG_KEEP_PINS) sched_fence();          // (signature kernels: no fence -- visit k: 0.8337 -> 0.8302 ms, every second one 0.8337)
-#endif
+        if (SIG == 0) sched_fence();          // (signature kernels: no fence -- visit k: 0.8337 -> 0.8302 ms, every second one 0.8337)
     }
 }
 template <int NJ, bool WANT_J, bool PLAIN, SegSig SIG, int J = 0, class CV>
@@ -195,8 +182,7 @@ RTB_HD void reg_core(const CV &cv, TL tail /* tail[k], k = 0..11 */, int frame, 
     reg_walk_steps<NJ, WANT_J, PLAIN, SIG>(cv, P, jac, jmv, c, s, d);
     // k_ik's chain views: the tail IS segment NJ of the table (no tool in IK), descriptor NJ carries its class
     if constexpr (SIG != 0) pose_mul_seg_by_sig<SIG, NJ>(P, cv);
-    else if constexpr (RTB_SEG_CLASSES && cv_has_trig<CV>::value) pose_mul_seg_cls(P, cv, NJ, cv.jmeta[NJ]);
-    else pose_mul_general<((PLAIN && RTB_POSE_T3_FMA && cv_has_trig<CV>::value) || cv_t3fma<CV>::value)>(P, [&](int k) { return tail[k]; });
+    else pose_mul_general<((PLAIN && cv_has_trig<CV>::value) || cv_t3fma<CV>::value)>(P, [&](int k) { return tail[k]; });
     sched_fence();
     reg_close_jacobian<NJ, WANT_J>(P, frame, jmv, jac);
 }

@@ -78,9 +78,6 @@ RTB_HD void kin_stage_T(const KinParams &kp, int lane, double *rows, Pose P)
 // Output rows are written once and never re-read by this kernel: non-temporal 16-byte stores
 // (global_store_dwordx4 ... nt) measured 0.0935 vs 0.105 ms per 1e6 Panda configurations on MI355X
 // (the bare access-pattern probe, scripts/roofline_probe.hip: 0.0868 vs 0.1013 ms).
-#ifndef RTB_NT_STORE
-#define RTB_NT_STORE 1
-#endif
 
 // STORAGE TYPE of the per-row arrays (q in; T, J, [T | J] out): double, or float for float32 tensors (rtbhip_fkine_jacob_f32 ...).  The arithmetic is
 // fp64 either way: a float is widened right after its load and a result is rounded once (round-to-nearest-even, the plain conversion) right
@@ -97,7 +94,7 @@ RTB_HD void store_pair_f32(float *__restrict__ dst, double a, double b)
     typedef float v2f __attribute__((ext_vector_type(2)));
     typedef v2f v2f_a4 __attribute__((aligned(4)));
     v2f w = {(float)a, (float)b};
-    if (NT && RTB_NT_STORE) __builtin_nontemporal_store(w, reinterpret_cast<v2f_a4 *>(dst));   // global_store_dwordx2 ... nt
+    if (NT) __builtin_nontemporal_store(w, reinterpret_cast<v2f_a4 *>(dst));   // global_store_dwordx2 ... nt
     else *reinterpret_cast<v2f_a4 *>(dst) = w;
 #else
     dst[0] = (float)a;
@@ -128,7 +125,7 @@ RTB_HD void kin_flush(const double *rows, int stride, int W, int ncfg, S *__rest
         double2 v;
         v.x = src[0];
         v.y = src[1];
-#if RTB_NT_STORE && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
         if (NT) {
             typedef double v2d __attribute__((ext_vector_type(2)));
             v2d w = {v.x, v.y};
@@ -168,7 +165,7 @@ RTB_HD void kin_flush_packed(const double *rowsT, const double *rowsJ, int strid
         double2 v;
         v.x = src[0];
         v.y = src[1];
-#if RTB_NT_STORE && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
         if (NT) {
             typedef double v2d __attribute__((ext_vector_type(2)));
             v2d w = {v.x, v.y};

@@ -30,16 +30,13 @@ RTB_HD double rcp_pivot(double d)
 // L_jk d_k of the textbook recurrence  d_j = a_jj - sum_k L_jk^2 d_k,  L_ij d_j = a_ij - sum_k L_ik L_jk d_k  are not re-formed term by term:
 // u_jk = L_jk d_k is the value the recurrence holds BEFORE it divides by the pivot, so it is kept (in the unused upper triangle, A[k][j]) and
 // every term is one fused multiply-add on it -- 56 multiplies fewer for N = 7, and each u_jk exact where L_jk d_k was a rounded product.
-#ifndef RTB_LDL_KEEP_U
-#define RTB_LDL_KEEP_U 1
-#endif
 // (fp contract(off), every fused multiply-add written: the recurrences are single chains the compiler would fuse the same way, but "would" is not
 // a construction -- see kin_device.h, mix_pp)
 template <int N, bool FAST = false>
 RTB_HD void ldl_factor(double (&A)[N][N], double (&dval)[N], double (&dinv)[N])
 {
 #pragma clang fp contract(off)
-    if constexpr (FAST && RTB_LDL_KEEP_U) {
+    if constexpr (FAST) {
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             double d = A[j][j];
@@ -64,7 +61,7 @@ RTB_HD void ldl_factor(double (&A)[N][N], double (&dval)[N], double (&dinv)[N])
 #pragma unroll
         for (int k = 0; k < j; ++k) d = __builtin_fma(-(A[j][k] * A[j][k]), dval[k], d);
         dval[j] = d;
-        dinv[j] = FAST ? rcp_pivot(d) : 1.0 / d;
+        dinv[j] = 1.0 / d;
 #pragma unroll
         for (int i = j + 1; i < N; ++i) {
             double v = A[i][j];

@@ -162,12 +162,6 @@ RTB_HD LinkBwd link_bwd(const LinkT &l)
     return o;
 }
 
-#ifndef RTB_RNE_NOFENCE
-#define RTB_RNE_NOFENCE 0
-#endif
-#ifndef RTB_RNE_PREFETCH
-#define RTB_RNE_PREFETCH 0
-#endif
 // ---- fused forms of the vector algebra of the recursions.  A sum of cross products and rotated vectors is accumulated as a
 // chain of fused multiply-adds (two per component and product) instead of "cross, cross, add, add": the same terms, one rounding
 // per product less, ~10 % fewer fp64 instructions per link.
@@ -289,12 +283,8 @@ RTB_HD V3 rot_fwd_add(const Rot &r, V3 v, V3 acc)   // acc + R v
 }
 
 // Everything one forward step reads from the link table and from the q / qd / qdd tile, fetched as ONE batch.
-// RTB_RNE_PREFETCH=1 (A/B knob, off): the batch of step j+1 is issued at the top of step j, so that the scalar-memory and LDS
-// round trips (about 300 cycles each; SQ counters: a third of the wave's lifetime in s_waitcnt) overlap a whole step of
-// arithmetic.  Measured on MI355X (1.25e6 Panda triples, kernel min of 30): 0.0648 ms without, 0.0798 ms with -- the second
-// operand set costs 26 VGPRs (182: two waves per SIMD instead of three), and forced back to three waves it spills (0.083 ms).
-// (s_waitcnt lgkmcnt counts scalar loads and LDS reads together and scalar loads return out of order: any wait is a wait for
-// everything outstanding, so a prefetch has to carry ALL of the next step's operands.)
+// (Issuing the batch of step j+1 at the top of step j measured 0.0648 -> 0.0798 ms per 1.25e6 Panda triples: the second operand set costs 26 VGPRs
+// and a wave per SIMD.  Dropping the fences between links: 182 VGPRs, two waves per SIMD.  profiles/retired_switches.md)
 struct FwdOps { LinkFwd f; double qj, qdj, qddj; };
 template <bool ALLREV, class LinkT, class InQ, class InQd, class InQdd>
 RTB_HD FwdOps fwd_ops(const LinkT &lt, int j, InQ qin, InQd qdin, InQdd qddin)
@@ -366,14 +356,10 @@ RTB_HD void rne_core(LinksP links, int n_rt, double (&st)[NJ > 0 ? NJ : RTBHIP_M
     // role -- so a pass at qd = 0 WITH gravity, `first` = 0, is Dynamics.gravload / the qd = NULL calls of rtbhip_rne)
     V3 w = v3(0, 0, 0), wd = v3(0, 0, 0), a = ACC ? grav : v3(0, 0, 0);
     double qddx = 0.0, qddy = 0.0;  // ne.c:311 lets gravity leak into qddv.x/.y for later links
-    constexpr bool PF = RTB_RNE_PREFETCH != 0 && NJ > 0;
     FwdOps cur = fwd_ops<ALLREV>(links[0], 0, qin, qdin, qddin);
 #pragma unroll
     for (int j = 0; j < n; ++j) {
-        if (!PF && j > 0) cur = fwd_ops<ALLREV>(links[j], j, qin, qdin, qddin);
-        FwdOps nxt = cur;
-        if (PF) sched_fence();     // cur's wait sits above this line, the next batch below it
-        if (PF && j + 1 < n) nxt = fwd_ops<ALLREV>(links[j + 1], j + 1, qin, qdin, qddin);
+        if (j > 0) cur = fwd_ops<ALLREV>(links[j], j, qin, qdin, qddin);
         const auto &li = links[j];                    // r and I: loaded inside the branches that need them
         const LinkFwd &l = cur.f;
         const bool pris = ALLREV ? false : (l.sigma != 0);
@@ -403,8 +389,7 @@ RTB_HD void rne_core(LinksP links, int n_rt, double (&st)[NJ > 0 ? NJ : RTBHIP_M
                 F[j] = l.m * ac;
                 Nn[j] = (flg[j] & kLinkIDiag) ? v3(li.I[0] * wd.x, li.I[4] * wd.y, li.I[8] * wd.z) : inertia_times(li, wd);
             }
-            cur = nxt;
-            if (!PF && !RTB_RNE_NOFENCE) sched_fence();
+            sched_fence();
             continue;
         }
         const V3 qdv = v3(0, 0, qdj);
@@ -476,8 +461,7 @@ RTB_HD void rne_core(LinksP links, int n_rt, double (&st)[NJ > 0 ? NJ : RTBHIP_M
         } else {
             Nn[j] = cross_add(w, inertia_times(li, w), inertia_times(li, wd));
         }
-        cur = nxt;
-        if (!PF && NJ > 0 && !RTB_RNE_NOFENCE) sched_fence();
+        if (NJ > 0) sched_fence();
     }
 
     // ---- backward recursion + joint projection (ne.c:354-492), fused
@@ -490,10 +474,7 @@ RTB_HD void rne_core(LinksP links, int n_rt, double (&st)[NJ > 0 ? NJ : RTBHIP_M
     for (int jj = 0; jj < n; ++jj) {
         const int j = n - 1 - jj;
         if (ACC && j < first) break;   // wave-uniform: the torques of the joints before `first` come from the mirror
-        if (!PF && jj > 0) bc = bwd_ops<ALLREV, FRICTION>(links[j], flg[j], j, qin, qdin, qddin);
-        BwdOps bn = bc;
-        if (PF) sched_fence();
-        if (PF && j > 0) bn = bwd_ops<ALLREV, FRICTION>(links[j - 1], flg[j - 1], j - 1, qin, qdin, qddin);
+        if (jj > 0) bc = bwd_ops<ALLREV, FRICTION>(links[j], flg[j], j, qin, qdin, qddin);
         const LinkBwd &l = bc.b;
         const bool last = (jj == 0);
         const bool pris = ALLREV ? false : (l.sigma != 0);
@@ -529,8 +510,7 @@ RTB_HD void rne_core(LinksP links, int n_rt, double (&st)[NJ > 0 ? NJ : RTBHIP_M
         }
         tau(j, t);
         f = fj; nn = nj; Rn = R; psn = ps; pmn = pm;
-        bc = bn;
-        if (!PF && NJ > 0 && !RTB_RNE_NOFENCE) sched_fence();
+        if (NJ > 0) sched_fence();
     }
     if constexpr (WOut::on && !ACC) {
         if (wout.wanted()) {           // wave-uniform

@@ -45,10 +45,7 @@ __device__ __forceinline__ void tile_copy(double *rows, int stride, int col_off,
     int f = lane;
     int r = f / n, c = f - r * n;
     const int da = kW / n, db = kW - da * n;
-#ifndef RTB_RNE_RT_BATCH
-#define RTB_RNE_RT_BATCH 1
-#endif
-    if (RTB_RNE_RT_BATCH && TO_LDS && gsrc) {
+    if (TO_LDS && gsrc) {
         // four loads in flight per trip (the trip count is a run-time value: a plain trip is load -> wait -> LDS store, one HBM round trip per 8 bytes)
         for (; f + 3 * kW < count; f += 4 * kW) {
             const double v0 = gsrc[f], v1 = gsrc[f + kW], v2 = gsrc[f + 2 * kW], v3 = gsrc[f + 3 * kW];
@@ -193,14 +190,9 @@ __device__ __forceinline__ void rne_tile(const RneParams &rp, ConstLinks links, 
         for (int k = 0; k < C; ++k) {
             const int f = lane + kW * k;
             const bool in = f < count;
-#if defined(RTB_RNE_PROBE_NOLOAD)   // timing probe only (wrong results): what the tile loads cost the wave's lifetime
-            r0[k] = in ? 1e-3 * f : 0.0; r1[k] = in ? 2e-3 * f : 0.0; r2[k] = in ? 3e-3 * f : 0.0;
-            (void)g0; (void)g1; (void)g2;
-#else
             r0[k] = in ? g0[f] : 0.0;
             r1[k] = (in && qd) ? g1[f] : 0.0;      // NULL qd / qdd = zeros (gravload, itorque)
             r2[k] = (in && qdd) ? g2[f] : 0.0;
-#endif
         }
 #pragma unroll
         for (int k = 0; k < C; ++k) {
@@ -305,24 +297,8 @@ __global__ __launch_bounds__(kW * WPB, RTB_RNE_WAVES) void k_rne_wpb(RneParams r
     rne_tile<NJ, MDH, ALLREV>(rp, (ConstLinks)links_g, NJ, stride, (int64_t)blockIdx.x * WPB + wave, q, qd, qdd, tau, lds + wave * kW * stride, lane);
 }
 
-// Persistent form of k_rne (rtbhip_tune("rne_persist", 1)): the grid is sized to the chip (three waves per SIMD) and every wave walks
-// tiles blockIdx.x, + gridDim.x, ... .  The loop the comment above warns about, made safe the way k_ik does it: the link-table pointer is
-// laundered once per trip, so the scalar loads stay inside the trip (the scalar cache serves them) instead of being hoisted into SGPRs that
-// do not exist.  What it buys: no workgroup dispatch between tiles (a slot that finishes a tile starts the next one at once).
-template <int NJ, bool MDH, bool ALLREV>
-__global__ __launch_bounds__(kW, RTB_RNE_WAVES) void k_rne_persist(RneParams rp, const DevLink *links_g, const double *__restrict__ q,
-                                                   const double *__restrict__ qd, const double *__restrict__ qdd,
-                                                   double *__restrict__ tau)
-{
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int64_t tiles = (rp.N + kW - 1) / kW;
-    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        ConstLinks l = (ConstLinks)links_g;
-        asm volatile("" : "+s"(l));
-        rne_tile<NJ, MDH, ALLREV>(rp, l, NJ, rne_stride(NJ), tile, q, qd, qdd, tau, lds, threadIdx.x);
-        __syncthreads();
-    }
-}
+// (A persistent grid-stride form of k_rne, the link-table pointer laundered once per trip, was built, measured slower and removed:
+// profiles/retired_switches.md)
 
 // qd = NULL on an all-revolute chain (Dynamics.gravload: qd = qdd = 0; Dynamics.itorque: qd = 0, no gravity): every link's
 // angular velocity is zero, so the forward recursion is the acceleration-only one of rne_device.h (ACC) from link 0 -- about
@@ -367,12 +343,11 @@ __global__ __launch_bounds__(kW) void k_rne_rt_f32(RneParams rp, const DevLink *
 }
 
 #if RTB_HOST_SIDE      // the launchers (the kernels above are also what jit.cpp hands to hipRTC, one instantiation at a time)
-namespace { int g_rne_tiles_per_wave = 1; int g_rne_persist = 0; int g_rne_wpb = 1; int g_rne_sig = 1; }
+namespace { int g_rne_tiles_per_wave = 1; int g_rne_wpb = 1; int g_rne_sig = 1; }
 int rne_sig_enabled() { return g_rne_sig; }
 void rne_tune(const char *key, int value)
 {
     if (std::string(key) == "rne_sig") g_rne_sig = value != 0;          // 0: never take a structure signature's instantiation (A/B, tests)
-    if (std::string(key) == "rne_persist") g_rne_persist = value < 0 ? 0 : (value > 4 ? 4 : value);      // waves per SIMD of the persistent grid, 0 = one tile per workgroup
     if (std::string(key) == "rne_wpb") g_rne_wpb = (value == 2 || value == 4) ? value : 1;
     if (std::string(key) == "rne_tiles_per_wave") g_rne_tiles_per_wave = value < 1 ? 1 : value;
 }
@@ -411,14 +386,14 @@ static void launch_nj(const Dyn *d, bool mdh, bool allrev, dim3 grid, size_t lds
                       const double *q, const double *qd, const double *qdd, double *tau, RneSig sig = 0)
 {
     if constexpr (NJ == 7) {
-        if (sig == kRneSigPanda && mdh && !g_rne_persist && g_rne_wpb == 1 && jit_builtin_enabled()) { launch_sig<7, true, kRneSigPanda>(grid, lds, s, rp, links, q, qd, qdd, tau); return; }
+        if (sig == kRneSigPanda && mdh && g_rne_wpb == 1 && jit_builtin_enabled()) { launch_sig<7, true, kRneSigPanda>(grid, lds, s, rp, links, q, qd, qdd, tau); return; }
     }
     if constexpr (NJ == 6) {
-        if (sig == kRneSigPuma560 && !mdh && !g_rne_persist && jit_builtin_enabled()) { launch_sig<6, false, kRneSigPuma560>(grid, lds, s, rp, links, q, qd, qdd, tau); return; }
+        if (sig == kRneSigPuma560 && !mdh && jit_builtin_enabled()) { launch_sig<6, false, kRneSigPuma560>(grid, lds, s, rp, links, q, qd, qdd, tau); return; }
     }
     // any other robot with a signature (all links revolute, n <= 8): its own instantiation of the same kernels, compiled at run time; until the
     // code object is there (or when hipRTC is not) the general kernels below serve -- the same numbers
-    if (sig && !rne_sig_builtin(NJ, mdh, sig) && jit_enabled() && !g_rne_persist && g_rne_wpb == 1) {
+    if (sig && !rne_sig_builtin(NJ, mdh, sig) && jit_enabled() && g_rne_wpb == 1) {
         const int variant = qd ? 0 : 1;
         if (hipFunction_t f = d->jit.get("rne_kernels.hip", variant, [&] { return rne_jit_expr(NJ, mdh, sig, variant); })) {
             RneParams rpv = rp;
@@ -431,15 +406,6 @@ static void launch_nj(const Dyn *d, bool mdh, bool allrev, dim3 grid, size_t lds
         if (mdh) hipLaunchKernelGGL((k_rne_atrest<NJ, true>), grid, dim3(kW), lds, s, rp, links, q, qdd, tau);
         else hipLaunchKernelGGL((k_rne_atrest<NJ, false>), grid, dim3(kW), lds, s, rp, links, q, qdd, tau);
         return;
-    }
-    if (g_rne_persist && allrev) {
-        int cus = 0;
-        if (device_cu_count(&cus) == RTBHIP_OK && (int64_t)grid.x > (int64_t)cus * 4 * g_rne_persist) {
-            const dim3 pg((unsigned)(cus * 4 * g_rne_persist));          // g_rne_persist waves per SIMD
-            if (mdh) hipLaunchKernelGGL((k_rne_persist<NJ, true, true>), pg, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
-            else hipLaunchKernelGGL((k_rne_persist<NJ, false, true>), pg, dim3(kW), lds, s, rp, links, q, qd, qdd, tau);
-            return;
-        }
     }
     if constexpr (NJ == 7) {                              // A/B knob, the benchmark's instantiation only
         if (g_rne_wpb > 1 && mdh && allrev) {
@@ -502,7 +468,7 @@ int launch_rne_f32(const Dyn *d, const DevLink *links, const float *q, const flo
     int64_t g = rt ? (tiles + g_rne_tiles_per_wave - 1) / g_rne_tiles_per_wave : tiles;
     if (g > 0x7fffffff) g = 0x7fffffff;
     dim3 grid((unsigned)g);
-    const RneSig sig = (g_rne_sig && !rt && !g_rne_persist && g_rne_wpb == 1) ? rne_signature(d->links.data(), d->n) : 0;
+    const RneSig sig = (g_rne_sig && !rt && g_rne_wpb == 1) ? rne_signature(d->links.data(), d->n) : 0;
     switch (rt ? 0 : d->n) {
     case 1: launch_nj_f32<1>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;
     case 2: launch_nj_f32<2>(mdh, allrev, grid, lds, s, rp, links, q, qd, qdd, tau, sig); break;

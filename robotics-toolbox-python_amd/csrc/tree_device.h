@@ -212,9 +212,6 @@ RTB_HD void tree_trig(GroupsP groups, InQ qin, double (&sn)[NG], double (&cs)[NG
 }
 
 // The two recursions with the sines and cosines supplied (the dynamics terms run several passes at one configuration).
-#ifndef RTB_TREE_ACC_ONLY
-#define RTB_TREE_ACC_ONLY 1      // 0: the unit-acceleration passes run the full recursion (A/B switch, scripts/build_variant.sh)
-#endif
 // VEL = false (compile-time): every joint velocity is zero -- the unit-acceleration passes that build the columns of M(q) (Dynamics.inertia,
 // the inertia half of Dynamics.accel).  All velocities stay exactly zero through the recursion, so everything that multiplies them is left
 // out: the two motion transforms of (v, w), the v x vJ terms, I v and the v x* (I v) forces -- about 90 of the ~210 operations a group's forward
@@ -223,12 +220,7 @@ RTB_HD void tree_trig(GroupsP groups, InQ qin, double (&sn)[NG], double (&cs)[NG
 // the column pass for joint i of a robot whose groups are numbered in joint order starts at group i: every group before it has zero
 // acceleration (it is no descendant of i), so its forward step is skipped (its saved state is written as zeros for the branches that hang
 // off it) and so is its backward step (M's entries above the diagonal come from the mirror).  dyn_device.h does the same for DH chains.
-#ifndef RTB_TREE_BILINEAR
-#define RTB_TREE_BILINEAR 1      // 0: Dynamics.coriolis by the polar form over full passes (two per column), the first implementation
-#endif
-#ifndef RTB_TREE_SKIP_PREFIX
-#define RTB_TREE_SKIP_PREFIX 1
-#endif
+// (The unit-acceleration passes running the full recursion, and from group 0, were the A/B baselines of these two: profiles/retired_switches.md)
 template <int NG, bool VEL = true, class KN = TreeNothing, class GroupsP, class InQ, class InQd, class InQdd, class Out, class Slot>
 RTB_HD void tree_rne_core(GroupsP groups, int nslots, const double (&sn)[NG], const double (&cs)[NG], V3 gravity, InQ qin, InQd qdin, InQdd qddin,
                           Out tau, Slot slot, int first = 0)
@@ -503,8 +495,8 @@ RTB_HD void tree_rne_lane(GroupsP groups, int nslots, V3 gravity, InQ qin, InQd 
 //   inertia   pass i = rne(q, 0, e_c, gravity 0) for the column c that group i moves (:752-758); kept: its entries j >= i, in the packed lower triangle
 //             mA[j (j + 1) / 2 + i] -- the kernel's flush mirrors them (M is symmetric; the mirrored half differs from the reference's
 //             separately rounded entries by rounding only), 21 instead of 36 doubles of LDS per lane for n = 6
-//   coriolis  mA = C(q, qd): column k = B(qd, e_k) from one two-field pass (tree_bilinear_core); RTB_TREE_BILINEAR = 0: the polar form /
-//             the reference's own scheme of rounds 1-3
+//   coriolis  mA = C(q, qd): column k = B(qd, e_k) from one two-field pass (tree_bilinear_core), which replaced the polar form /
+//             the reference's own scheme of rounds 1-3 (profiles/retired_switches.md)
 //   accel     mA[0..n) = qdd = M^-1 (torque - rne(q, qd, 0))          (:492-505; M's lower triangle, LDL^T)
 template <int NG>
 RTB_HD void tree_opaque(double (&sn)[NG], double (&cs)[NG])
@@ -515,18 +507,12 @@ RTB_HD void tree_opaque(double (&sn)[NG], double (&cs)[NG])
 #endif
 }
 
-// a[j] = v / a[j] += v for a wave-uniform run-time j (the tau column of a group) without indexing the register array
+// a[j] = v for a wave-uniform run-time j (the tau column of a group) without indexing the register array
 template <int NG>
 RTB_HD void tree_put(double (&a)[NG], int j, double v)
 {
 #pragma unroll
     for (int k = 0; k < NG; ++k) a[k] = (j == k) ? v : a[k];
-}
-template <int NG>
-RTB_HD void tree_add(double (&a)[NG], int j, double v)
-{
-#pragma unroll
-    for (int k = 0; k < NG; ++k) a[k] += (j == k) ? v : 0.0;
 }
 
 // group j moves q column j for every j: the robot is numbered in group order (wave-uniform)
@@ -563,14 +549,13 @@ RTB_HD void tree_dyn_lane(GroupsP groups, int nslots, const double *mine, double
     // in group order (Robot.py:1875-1893): row jq_i of the reference's M is row i of Mp.  For a robot numbered in group order (every URDF robot,
     // every robot whose jindex was assigned automatically) the two coincide; otherwise the inertia kernel's flush permutes the rows and accel
     // permutes its right-hand side (below) -- tree_row_position().
-    constexpr bool skip = RTB_TREE_SKIP_PREFIX && RTB_TREE_ACC_ONLY;
     if (MODE == kDynInertia) {
 #pragma unroll 1
         for (int i = 0; i < NG; ++i) {
             tree_opaque<NG>(sn, cs);
             const int ci = kPlain ? i : jm_jq(groups[i].jmeta);
-            tree_rne_core<NG, !RTB_TREE_ACC_ONLY, KN>(groups, nslots, sn, cs, zero, qin, none, [&](int c) { return c == ci ? 1.0 : 0.0; },
-                                     [&](int j, double v) { if (j >= i) mA[j * (j + 1) / 2 + i] = v; }, slot, skip ? i : 0);
+            tree_rne_core<NG, false, KN>(groups, nslots, sn, cs, zero, qin, none, [&](int c) { return c == ci ? 1.0 : 0.0; },
+                                     [&](int j, double v) { if (j >= i) mA[j * (j + 1) / 2 + i] = v; }, slot, i);
         }
     }
     if (MODE == kDynAccel) {
@@ -591,8 +576,8 @@ RTB_HD void tree_dyn_lane(GroupsP groups, int nslots, const double *mine, double
         for (int i = 0; i < NG; ++i) {
             tree_opaque<NG>(sn, cs);
             const int ci = kPlain ? i : jm_jq(groups[i].jmeta);
-            tree_rne_core<NG, !RTB_TREE_ACC_ONLY, KN>(groups, nslots, sn, cs, zero, qin, none, [&](int c) { return c == ci ? 1.0 : 0.0; },
-                                     [&](int j, double v) { if (j >= i) mA[j * (j + 1) / 2 + i] = v; }, slot, skip ? i : 0);
+            tree_rne_core<NG, false, KN>(groups, nslots, sn, cs, zero, qin, none, [&](int c) { return c == ci ? 1.0 : 0.0; },
+                                     [&](int j, double v) { if (j >= i) mA[j * (j + 1) / 2 + i] = v; }, slot, i);
         }
         double x[NG], M[NG][NG];
 #pragma unroll
@@ -604,7 +589,6 @@ RTB_HD void tree_dyn_lane(GroupsP groups, int nslots, const double *mine, double
         for (int j = 0; j < NG; ++j) mA[j] = x[j];
     }
     if (MODE == kDynCoriolis) {
-#if RTB_TREE_BILINEAR
         // column k = B(qd, e_k), one two-field pass each (tree_bilinear_core)
         bool ordered = true;
 #pragma unroll
@@ -615,66 +599,6 @@ RTB_HD void tree_dyn_lane(GroupsP groups, int nslots, const double *mine, double
             tree_bilinear_core<NG, KN>(groups, nslots, sn, cs, qin, [&](int j) { return mine[NG + j]; }, k,
                                    [&](int r, double v) { mA[r * NG + k] = 0.5 * v; }, slot, ordered ? k : 0);
         }
-#else
-        // dyn_device.h, the same two schemes and the same per-row choice between them
-        double qdv[NG], vmax = 0.0;
-#pragma unroll
-        for (int j = 0; j < NG; ++j) { qdv[j] = mine[NG + j]; vmax = fmax(vmax, fabs(qdv[j])); }
-        int ex = 0;
-        const double mant = frexp(vmax, &ex);
-        if (mant == 0.5) ex -= 1;
-        if (!(vmax > 0.0) || !(vmax < 1.7e308)) ex = 0;
-        ex = ex > 400 ? 400 : (ex < -400 ? -400 : ex);
-        const double sc = ldexp(1.0, ex);
-        const double inv4s = vmax > 0.0 || vmax != vmax ? 0.25 / sc : 0.0;
-        bool wide = false;
-#pragma unroll
-        for (int j = 0; j < NG; ++j) wide = wide || (qdv[j] != 0.0 && fabs(qdv[j]) * 65536.0 < vmax);
-        auto polar = [&]() {
-#pragma unroll 1
-            for (int k = 0; k < NG; ++k) {
-                tree_opaque<NG>(sn, cs);
-                tree_rne_core<NG>(groups, nslots, sn, cs, zero, qin, [&](int j) { return j == k ? qdv[j] + sc : qdv[j]; }, none,
-                                  [&](int r, double v) { mA[r * NG + k] = v; }, slot);
-                tree_opaque<NG>(sn, cs);
-                tree_rne_core<NG>(groups, nslots, sn, cs, zero, qin, [&](int j) { return j == k ? qdv[j] - sc : qdv[j]; }, none,
-                                  [&](int r, double v) { mA[r * NG + k] = (mA[r * NG + k] - v) * inv4s; }, slot);
-            }
-        };
-        auto reference_scheme = [&]() {
-            double S = 0.0, U[NG];
-#pragma unroll
-            for (int j = 0; j < NG; ++j) { S += qdv[j]; U[j] = 0.0; }
-#pragma unroll 1
-            for (int i = 0; i < NG; ++i) {
-                const double qdi = dyn_pick<NG>(qdv, i), wi = 2.0 * qdi - 0.5 * S;
-                tree_opaque<NG>(sn, cs);
-                tree_rne_core<NG>(groups, nslots, sn, cs, zero, qin, [&](int j) { return j == i ? 1.0 : 0.0; }, none,
-                                  [&](int r, double v) { mA[r * NG + i] = v * wi; tree_add<NG>(U, r, v * qdi); }, slot);
-            }
-#pragma unroll
-            for (int r = 0; r < NG; ++r)
-#pragma unroll
-                for (int c = 0; c < NG; ++c) mA[r * NG + c] -= 0.5 * U[r];
-#pragma unroll 1
-            for (int i = 0; i < NG; ++i) {
-#pragma unroll 1
-                for (int j = i + 1; j < NG; ++j) {
-                    const double hi = 0.5 * dyn_pick<NG>(qdv, i), hj = 0.5 * dyn_pick<NG>(qdv, j);
-                    tree_opaque<NG>(sn, cs);
-                    tree_rne_core<NG>(groups, nslots, sn, cs, zero, qin, [&](int k) { return (k == i || k == j) ? 1.0 : 0.0; }, none,
-                                      [&](int r, double tq) {
-                                          mA[r * NG + j] += tq * hi;
-                                          mA[r * NG + i] += tq * hj;
-                                      }, slot);
-                }
-            }
-        };
-        polar();                                   // every lane; wide rows redo their tile below (dyn_device.h)
-        if (wave_any(wide)) {
-            if (wide) reference_scheme();
-        }
-#endif
     }
 }
 

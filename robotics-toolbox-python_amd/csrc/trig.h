@@ -109,9 +109,6 @@ RTB_HD void sched_fence()
 // wave or that are compute-bound lose 1-3 % with it (Hessian tile, k_partial, the fleet, RNE, the dynamics terms) and keep
 // the identity mapping.  Leap-frogging chunks of 16 or 128 consecutive tiles per XCD instead of eighths: slower and as
 // unsteady as the identity (0.082-0.090 ms against a steady 0.080).  A bijection of [0, grid) for any grid size.
-#ifndef RTB_XCD_REMAP
-#define RTB_XCD_REMAP 1
-#endif
 RTB_HD unsigned xcd_tile_of(unsigned g, unsigned b)     // grid size, workgroup id -> tile
 {
     const unsigned x = b & 7u, q8 = g >> 3, r8 = g & 7u;
@@ -120,11 +117,7 @@ RTB_HD unsigned xcd_tile_of(unsigned g, unsigned b)     // grid size, workgroup 
 #if defined(__HIPCC__)
 __device__ __forceinline__ unsigned xcd_tile()
 {
-#if RTB_XCD_REMAP
     return xcd_tile_of(gridDim.x, blockIdx.x);
-#else
-    return blockIdx.x;
-#endif
 }
 #endif
 

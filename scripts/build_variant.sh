@@ -1,6 +1,6 @@
 #!/bin/bash
 # build_variant.sh SRC NAME -DFOO=1 ... : robotics-toolbox-python_amd/lib/variants/NAME.so = the product's objects (build/obj, from build_lib) with
-# csrc/SRC.hip recompiled under the extra defines -- an A/B library for RTBHIP_LIB without a full rebuild (build_ik_variant.sh for any kernel file).
+# csrc/SRC.hip recompiled under the extra defines -- an A/B library for RTBHIP_LIB without a full rebuild.
 set -e
 R=$(cd $(dirname $0)/.. && pwd)
 src=$1; name=$2; shift 2

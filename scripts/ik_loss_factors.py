@@ -51,5 +51,5 @@ torch.cuda.synchronize()
 ms, _, _ = sustained_ms(run)
 its = float(res["out"][2].sum())
 out = bs.ik_loss_factors(run, its, ms)
-out.update({"kernel_avg_ms": ms, "lm_iterations": its, "kernel": "k_ik<7,0,13,kIkSigPandaETS> (flat schedule)"})
+out.update({"kernel_avg_ms": ms, "lm_iterations": its, "kernel": "k_ik<7,0,13,kSigPandaETS> (flat schedule)"})
 print(json.dumps(out))

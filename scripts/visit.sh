@@ -76,7 +76,7 @@ if has ikab; then
   timeout ${IKAB_TIMEOUT:-900} python scripts/ik_ab.py $IKAB_ARGS > $O/ik_ab.jsonl 2> $O/ik_ab.err; cut -c1-260 $O/ik_ab.jsonl | tail -60; tail -3 $O/ik_ab.err
 fi
 if has libab; then
-  # A/B LIBRARIES of k_ik (robotics-toolbox-python_amd/lib/variants/*.so from scripts/build_ik_variant.sh), one process per library and round, interleaved
+  # A/B LIBRARIES of k_ik (robotics-toolbox-python_amd/lib/variants/*.so from scripts/build_variant.sh ik_kernels), one process per library and round, interleaved
   : > $O/ik_lib_ab.jsonl
   for r in $(seq 1 ${LIBAB_ROUNDS:-3}); do
     for v in product $VARIANTS; do

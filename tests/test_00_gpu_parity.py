@@ -704,7 +704,7 @@ def test_ik_kernel_specialisations_agree():
 
 def test_ik_structure_signature_kernel_returns_the_general_kernel_s_bits():
     """The Panda's chain has a structure signature k_ik is instantiated for (six quarter turns about x, translations on some axes, the flange
-    rotation: csrc/ik_kernels.hip kIkSigPandaETS; its constant segments are then multiplied in the form of their class, csrc/kin_device.h).
+    rotation: csrc/kin_reg.h kSigPandaETS; its constant segments are then multiplied in the form of their class, csrc/kin_device.h).
     Every structured product is the general product with its exact zeros dropped, operation for operation: q, E, success, iterations and
     searches must be BIT-IDENTICAL to the general kernel's (rtbhip_tune "ik_sig" = 0), in both solver flavours and with a weighted mask (which
     never takes the specialised kernel).  A chain with another signature is not affected by the switch."""

@@ -39,7 +39,7 @@ def test_library_reports_the_embedded_sources():
 
 
 def test_builtin_robots_ask_for_nothing():
-    assert jit.names(rtbhip.models.Panda().ets())[0] == []                     # kIkSigPandaETS
+    assert jit.names(rtbhip.models.Panda().ets())[0] == []                     # kSigPandaETS
     assert jit.names(rtbhip.models.DH.Panda())[0] == []                        # kRneSigPanda
     assert jit.names(rtbhip.models.DH.Puma560())[0] == []                      # kRneSigPuma560
     assert jit.names(rtbhip.urdf.load("UR5").erobot())[0] == []                # kTreeSigUR

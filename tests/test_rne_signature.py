@@ -115,3 +115,25 @@ def test_switch_leaves_a_robot_with_another_signature_alone():
 def test_gpu_signature_kernels_equal_the_general_kernels(name):
     out, _ = _both(_models()[name], 20000, 7)
     _compare(out)
+
+
+@pytest.mark.gpu
+def test_gpu_launch_shape_knobs_leave_the_torques_alone():
+    """rtbhip_tune("rne_persist") chose k_rne_persist until that kernel was removed (profiles/retired_switches.md): an unknown key now -- accepted, and
+    without effect.  "rne_wpb" still chooses k_rne_wpb for the modified-DH Panda (four waves per workgroup: at these sizes one workgroup whose later
+    waves find their tiles empty): the same torques, bit for bit.  Standard-DH Puma560 and modified-DH Panda; N = 1, and N = 65 = a full tile and a
+    ragged one."""
+    import torch
+    rng = np.random.default_rng(11)
+    for rob in _models().values():
+        for N in (1, 65):
+            q, qd, qdd = (torch.from_numpy(rng.normal(size=(N, rob.n))).cuda() for _ in range(3))
+            want = rob.rne(q, qd, qdd)
+            try:
+                rtbhip.tune("rne_persist", 2)
+                rtbhip.tune("rne_wpb", 4)
+                got = rob.rne(q, qd, qdd)
+            finally:
+                rtbhip.tune("rne_persist", 0)
+                rtbhip.tune("rne_wpb", 1)
+            assert torch.equal(got, want), (type(rob).__name__, N)

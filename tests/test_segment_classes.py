@@ -71,7 +71,7 @@ def test_the_panda_is_six_quarter_turns_and_a_flange_rotation():
     assert [g[0] for g in got] == ["identity", "RxN", "RxP", "RxP", "RxN", "RxP", "RxP", "Rz"], got
     # C_2 = Rx(pi/2) tz(0.316): t = (0, -0.316, 1.9e-17) -- the tiny component is NOT dropped
     assert got[2][1] == 0b110 and got[1][1] == 0 and got[7][1] == 0b100
-    # ... which is the signature k_ik has a straight-line instantiation for (ik_kernels.hip: kIkSigPandaETS)
+    # ... which is the signature k_ik has a straight-line instantiation for (kin_reg.h: kSigPandaETS)
     import cpu_backend
     with cpu_backend.installed():
         ets = rtbhip.models.Panda().ets()                 # (kept alive: the handle dies with its ETS)
@@ -118,12 +118,12 @@ def test_random_robots_fkine_through_the_ik_walk_equals_the_oracle():
 
 
 def test_signatures_k_ik_is_instantiated_for_are_those_robots_signatures():
-    """csrc/ik_kernels.hip: kIkSigPandaETS (also the DH Panda lowered to an ETS), kIkSigPandaURDF, kIkSigUR -- read from the source, compared with what
+    """csrc/kin_reg.h: kSigPandaETS (also the DH Panda lowered to an ETS), kSigPandaURDF, kSigUR -- read from the source, compared with what
     the chain compiler computes for the robots they are named after (a constant that drifts from its robot would silently fall back to the general kernel)"""
     import os, re
     import cpu_backend
     from rtbhip import urdf
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "robotics-toolbox-python_amd", "csrc", "ik_kernels.hip")).read()
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "robotics-toolbox-python_amd", "csrc", "kin_reg.h")).read()
     cls = {"kSeg" + n[0].upper() + n[1:]: i for i, n in enumerate(NAMES)}
     cls.update({"kSegPermA": 11, "kSegPermB": 12})
 
@@ -135,9 +135,9 @@ def test_signatures_k_ik_is_instantiated_for_are_those_robots_signatures():
         return sig
     with cpu_backend.installed():
         lib = emu_harness.lib()
-        robots = {"kIkSigPandaETS": [rtbhip.models.Panda().ets(), rtbhip.models.DH.Panda().ets()],
-                  "kIkSigPandaURDF": [urdf.load("Panda").ets()],
-                  "kIkSigUR": [urdf.load(n).ets(end="tool0") for n in ("UR3", "UR5", "UR10")]}
+        robots = {"kSigPandaETS": [rtbhip.models.Panda().ets(), rtbhip.models.DH.Panda().ets()],
+                  "kSigPandaURDF": [urdf.load("Panda").ets()],
+                  "kSigUR": [urdf.load(n).ets(end="tool0") for n in ("UR3", "UR5", "UR10")]}
         for name, chains_ in robots.items():
             for e in chains_:
                 assert lib.emu_chain_signature(C.c_uint64(e._handle())) == constant(name), name
