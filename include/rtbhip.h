@@ -306,6 +306,22 @@ int rtbhip_rne(rtbhip_dyn_t dyn, const double *q, const double *qd, const double
 int rtbhip_rne_f32(rtbhip_dyn_t dyn, const float *q, const float *qd, const float *qdd, int64_t N,
                    const double *grav3, const double *fext6, float *tau, int32_t mem, void *stream);
 
+/* VECTOR-JACOBIAN PRODUCT of rtbhip_rne -- the backward pass of a loss on the torques; no reference counterpart.  What is differentiated is
+ * the recursion of newton_euler as rtbhip_rne evaluates it: the forward pass (ne.c:133-348), the backward pass and the joint projection
+ * (ne.c:354-492), behind DHRobot.rne (robot/DHRobot.py:1373-1456).  gtau (N,n) is the loss's gradient with respect to tau;
+ *   gq[i,k] = sum_j gtau[i,j] d tau_j / d q_k,   gqd and gqdd likewise (each (N,n)).
+ * Any of gq / gqd / gqdd may be NULL -- that gradient is not written (the sweeps the three share run either way) -- but not all three.  q, qd, qdd, grav3 and fext6 are
+ * those of the forward call (qd and / or qdd NULL = zeros); gravity and the external wrench are constants of the differentiation.  The
+ * joint-space terms of ne.c:464-492 contribute G^2 Jm to gqdd and G^2 B to gqd; the Coulomb term has derivative zero (the gradient at qd_j = 0
+ * is that of the friction-free side).  One fused kernel, one launch: chains of 1..8 joints in registers, 9..32 through a run-time-n kernel.
+ * Chains whose links are all revolute; RTBHIP_EINVAL for a chain with a prismatic joint. */
+int rtbhip_rne_vjp(rtbhip_dyn_t dyn, const double *q, const double *qd, const double *qdd, int64_t N, const double *grav3, const double *fext6,
+                   const double *gtau, double *gq, double *gqd, double *gqdd, int32_t mem, void *stream);
+/* ... with q, qd, qdd, gtau and the gradients held as float in device memory (see rtbhip_rne_f32: values are widened after their load, the
+ * arithmetic is fp64, each gradient is rounded once; mem must be RTBHIP_MEM_DEVICE). */
+int rtbhip_rne_vjp_f32(rtbhip_dyn_t dyn, const float *q, const float *qd, const float *qdd, int64_t N, const double *grav3, const double *fext6,
+                       const float *gtau, float *gq, float *gqd, float *gqdd, int32_t mem, void *stream);
+
 /* DHRobot.rne(..., base_wrench=True) -> rne_python (robot/DHRobot.py:1409-1412, 1765-1770), batched: the torques as rtbhip_rne and
  * wbase (N,6) = [R_1 f_1, R_1 n_1], the force and moment the base exerts on link 1, rotated into frame 0 -- what the backward
  * recursion of rtbhip_rne holds when it ends; the moment refers to the origin of frame 0 (standard DH) / of frame 1 (modified DH).

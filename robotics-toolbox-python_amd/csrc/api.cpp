@@ -639,6 +639,48 @@ int rne_entry(const char *fn, rtbhip_dyn_t dyn, const R *q, const R *qd, const R
     return rne_run(d, links, q, qd, qdd, N, grav3, fext6, tau, wbase, want_wbase, mem, stream);
 }
 
+}  // namespace
+// the launchers of the inverse-dynamics adjoint (rne_vjp_kernels.hip); declared here for the reason launch_kin_vjp is, and WEAK: a library linked
+// from this object without that unit (the CPU replay of the test suite) still loads, and refuses the two entry points
+__attribute__((weak)) int launch_rne_vjp(const Dyn *d, const DevLink *links, const double *q, const double *qd, const double *qdd, int64_t N,
+                                         const double *grav3, const double *fext6, const double *gtau, double *gq, double *gqd, double *gqdd,
+                                         hipStream_t s);
+__attribute__((weak)) int launch_rne_vjp_f32(const Dyn *d, const DevLink *links, const float *q, const float *qd, const float *qdd, int64_t N,
+                                             const double *grav3, const double *fext6, const float *gtau, float *gq, float *gqd, float *gqdd,
+                                             hipStream_t s);
+namespace {
+
+// rtbhip_rne_vjp / rtbhip_rne_vjp_f32: the gradient of a loss on rtbhip_rne's torques with respect to q, qd and qdd (k_rne_vjp)
+template <class R>
+int rne_vjp_entry(const char *fn, rtbhip_dyn_t dyn, const R *q, const R *qd, const R *qdd, int64_t N, const double *grav3, const double *fext6,
+                  const R *gtau, R *gq, R *gqd, R *gqdd, int32_t mem, void *stream)
+{
+    RTB_TRACE(fn);
+    const std::shared_ptr<Dyn> d_owner = dyn_from_handle(dyn);
+    Dyn *d = d_owner.get();
+    if (!d) return refuse(fn, "unknown dyn handle");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    RTB_TRY(check_row_type<R>(fn, mem));
+    if (N == 0) return RTBHIP_OK;                            // an empty batch: no pointer is looked at
+    if (!gtau) return refuse(fn, "NULL gtau");               // qd / qdd may be NULL (= zeros)
+    if (!gq && !gqd && !gqdd) return refuse(fn, "gq, gqd and gqdd are all NULL: there is nothing to compute");
+    if (!grav3) return refuse(fn, "NULL gravity");           // (read on the host, as rtbhip_rne's)
+    for (const DevLink &l : d->links)
+        if (l.sigma != 0) return refuse(fn, "chain has a prismatic joint");
+    const bool built = std::is_same<R, float>::value ? launch_rne_vjp_f32 != nullptr : launch_rne_vjp != nullptr;
+    if (!built) return refuse(fn, "not built into this library");
+    const DevLink *links = nullptr;
+    RTB_TRY(dyn_device_links(d, &links));
+    const size_t bytes = (size_t)N * (size_t)d->n * sizeof(R);
+    Staged st(mem, stream);
+    const R *dq = st.in(q, bytes), *dqd = st.in(qd, bytes), *dqdd = st.in(qdd, bytes), *dg = st.in(gtau, bytes);
+    R *dgq = st.out(gq, bytes), *dgqd = st.out(gqd, bytes), *dgqdd = st.out(gqdd, bytes);
+    RTB_TRY(st.status());
+    if constexpr (std::is_same<R, float>::value) return st.finish(launch_rne_vjp_f32(d, links, dq, dqd, dqdd, N, grav3, fext6, dg, dgq, dgqd, dgqdd, st.stream()));
+    else return st.finish(launch_rne_vjp(d, links, dq, dqd, dqdd, N, grav3, fext6, dg, dgq, dgqd, dgqdd, st.stream()));
+}
+
 /* Dynamics.inertia / coriolis / accel (robot/Dynamics.py:704-861, 424-509) of a DH arm (kind "dyn": dyn_from_handle, dyn_device_links,
    launch_dyn) and of an ETS robot's link tree over Robot.rne (kind "tree").  mode: 0 inertia, 1 coriolis, 2 accel. */
 template <class Obj, class Table>
@@ -1243,6 +1285,18 @@ int rtbhip_rne_base_wrench(rtbhip_dyn_t dyn, const double *q, const double *qd, 
                            const double *grav3, const double *fext6, double *tau, double *wbase, int32_t mem, void *stream)
 {
     return rne_entry<double>("rne_base_wrench", dyn, q, qd, qdd, N, grav3, fext6, tau, wbase, true, mem, stream);
+}
+
+int rtbhip_rne_vjp(rtbhip_dyn_t dyn, const double *q, const double *qd, const double *qdd, int64_t N, const double *grav3, const double *fext6,
+                   const double *gtau, double *gq, double *gqd, double *gqdd, int32_t mem, void *stream)
+{
+    return rne_vjp_entry<double>("rne_vjp", dyn, q, qd, qdd, N, grav3, fext6, gtau, gq, gqd, gqdd, mem, stream);
+}
+
+int rtbhip_rne_vjp_f32(rtbhip_dyn_t dyn, const float *q, const float *qd, const float *qdd, int64_t N, const double *grav3, const double *fext6,
+                       const float *gtau, float *gq, float *gqd, float *gqdd, int32_t mem, void *stream)
+{
+    return rne_vjp_entry<float>("rne_vjp_f32", dyn, q, qd, qdd, N, grav3, fext6, gtau, gq, gqd, gqdd, mem, stream);
 }
 
 int rtbhip_tree_create(const rtbhip_tree_group *groups, int32_t ng, rtbhip_tree_t *tree)

@@ -56,6 +56,10 @@ class _sp(C.c_void_p):
         return C.c_void_p.from_param(value)
 
 
+class _sq(_sp):
+    """`void *stream` of rtbhip_rne_vjp / rtbhip_rne_vjp_f32: as _sp, a type of its own; their refusal rows and census are in tests/test_rne_vjp.py."""
+
+
 # name -> (restype, argtypes); must list every symbol include/rtbhip.h declares
 SIGNATURES = {
     "rtbhip_last_error": (C.c_char_p, []),
@@ -100,6 +104,8 @@ SIGNATURES = {
     "rtbhip_dyn_destroy": (C.c_int, [_u64]),
     "rtbhip_rne": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
     "rtbhip_rne_f32": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "rtbhip_rne_vjp": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _sq]),
+    "rtbhip_rne_vjp_f32": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _sq]),
     "rtbhip_rne_base_wrench": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
     "rtbhip_jacob_dot": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_jacob0_dot_analytical": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),

@@ -1,10 +1,17 @@
-"""Gradients of ETS.eval / fkine, ETS.jacob0 and the two-array ETS.fkine_jacob0 with respect to a CUDA q (torch.autograd).
+"""Gradients of ETS.eval / fkine, ETS.jacob0 and the two-array ETS.fkine_jacob0 with respect to a CUDA q, and of DHRobot.rne (gravload, itorque) and
+DHRobot.accel with respect to their CUDA inputs (torch.autograd).
 
 Imported by rtbhip/et.py only when a call's q is a CUDA tensor with requires_grad while gradients are enabled (`_lib.wants_grad`), so torch is a
 dependency of this module alone.  One Function: its forward is the ordinary call (gradients are off inside a Function's forward, so the
 front end takes the path it always took), its backward one launch of rtbhip_fkine_jacob_vjp(_f32) on the current stream -- for fkine_jacob0
 both outputs hang off one node, so a loss on T and J costs one backward launch.  The backward is not itself differentiable (no double
-backward).  Not differentiable at all, and unchanged: jacobe, frame=1, packed=True, out=, hessian0, the IK solvers, the dynamics."""
+backward).  Not differentiable at all, and unchanged: jacobe, frame=1, packed=True, out=, hessian0, the IK solvers.
+
+The dynamics (rtbhip/dh.py routes here for all-revolute DH chains, never with base_wrench=True): _RneVJP's backward is one launch of
+rtbhip_rne_vjp(_f32), which returns the gradients autograd asks for (ctx.needs_input_grad) and no others.  _AccelVJP needs no kernel of its
+own: with qdd = accel(q, qd, torque) and g its incoming gradient, lambda = M^-1 g is one more accel call (qd = 0, no gravity; M is symmetric for
+an all-revolute chain), the gradient of torque is lambda and those of q and qd are rne_vjp's at (q, qd, qdd) for gtau = -lambda (the implicit
+function theorem on  rne(q, qd, qdd) = torque).  inertia, coriolis, the ETS robots' dynamics: not differentiable, unchanged."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -58,3 +65,72 @@ def differentiable(ets, what, q, base, tool):
         with torch.no_grad():
             return _ordinary(ets, what, q, base, tool)
     return _KinVJP.apply(q, ets, what, small(base, 16), small(tool, 16))
+
+
+# ---------------------------------------------------------------- the dynamics of a DH robot
+def _rne_vjp(robot, q, qd, qdd, gtau, gravity, fext, want):
+    """rtbhip_rne_vjp(_f32) on the current stream: the gradients named by `want` (three booleans), each shaped like its input; None for the others"""
+    n = robot.n
+    rows = lambda x: None if x is None else x.detach().reshape(-1, n).contiguous()
+    q2, qd2, qdd2 = rows(q), rows(qd), rows(qdd)
+    g2 = gtau.detach().to(q2.dtype).reshape(-1, n).contiguous()
+    N = q2.shape[0]
+    outs = [torch.empty_like(q2) if w else None for w in want]
+    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    fn = lib().rtbhip_rne_vjp_f32 if q2.element_size() == 4 else lib().rtbhip_rne_vjp
+    f = None if fext is None else small(fext, 6)
+    check(fn(robot._dyn_handle(), ptr(q2), ptr(qd2), ptr(qdd2), N, host_ptr(robot._gravity_c(gravity)), host_ptr(f), ptr(g2),
+             ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), MEM_DEVICE, current_stream_ptr()))
+    return [None if o is None else o.reshape(x.shape) for o, x in zip(outs, (q, qd, qdd))]
+
+
+class _RneVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, qd, qdd, robot, gravity, fext):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, qd, qdd)
+        ctx.robot, ctx.gravity, ctx.fext = robot, gravity, fext
+        return robot.rne(q, qd, qdd, gravity=gravity, fext=fext)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gtau):
+        q, qd, qdd = ctx.saved_tensors
+        want = [bool(w) for w in ctx.needs_input_grad[:3]]
+        if gtau is None or not any(want):
+            return None, None, None, None, None, None
+        gq, gqd, gqdd = _rne_vjp(ctx.robot, q, qd, qdd, gtau, ctx.gravity, ctx.fext, want)
+        return gq, gqd, gqdd, None, None, None
+
+
+class _AccelVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, qd, torque, robot, gravity):
+        ctx.set_materialize_grads(False)
+        qdd = robot.accel(q, qd, torque, gravity=gravity)
+        ctx.save_for_backward(q, qd, qdd)
+        ctx.robot, ctx.gravity = robot, gravity
+        return qdd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        q, qd, qdd = ctx.saved_tensors
+        want = [bool(w) for w in ctx.needs_input_grad[:3]]
+        if g is None or not any(want):
+            return None, None, None, None, None
+        lam = ctx.robot.accel(q.detach(), torch.zeros_like(qd), g.to(q.dtype).reshape(q.shape).contiguous(), gravity=[0.0, 0.0, 0.0])       # M^-1 g
+        gq = gqd = None
+        if want[0] or want[1]:
+            gq, gqd, _ = _rne_vjp(ctx.robot, q, qd, qdd, -lam, ctx.gravity, None, [want[0], want[1], False])
+        return gq, gqd, (lam.reshape(q.shape) if want[2] else None), None, None
+
+
+def differentiable_rne(robot, q, qd, qdd, gravity, fext):
+    """DHRobot.rne(q, qd, qdd, gravity=, fext=) attached to the autograd graph of its tensor inputs (qd / qdd may be None)"""
+    return _RneVJP.apply(q, qd, qdd, robot, gravity, fext)
+
+
+def differentiable_accel(robot, q, qd, torque, gravity):
+    """DHRobot.accel(q, qd, torque, gravity=) attached to the autograd graph of its inputs"""
+    return _AccelVJP.apply(q, qd, torque, robot, gravity)

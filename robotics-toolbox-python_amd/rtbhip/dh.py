@@ -523,13 +523,22 @@ class DHRobot(RobotKinematics):
             g = self.base[:3, :3].T @ g          # reference robot/DHRobot.py:1431-1433
         return np.ascontiguousarray(-g)          # "we negate gravity here" robot/DHRobot.py:1449
 
+    def _wants_grad(self, *inputs):
+        """a call on these inputs records an autograd node: one of them asks for it (_lib.wants_grad) and every link is revolute"""
+        return any(_lib.wants_grad(x) for x in inputs) and all(l.sigma == 0 for l in self.links)
+
     def rne(self, q, qd=None, qdd=None, gravity=None, fext=None, base_wrench=False):
         """Inverse dynamics tau(q, qd, qdd): (n,) or (N,n)
         (reference robot/DHRobot.py:1373-1456 -> frne.frne core/frne.c:106-230).
         qd / qdd = None means zeros (no zero arrays are read by the kernel).
         float32 CUDA tensors (all of q, qd, qdd; a mix is a TypeError) give a float32 tau: rtbhip_rne_f32 -- fp64 arithmetic, each torque rounded once,
         equal to `rne(q.double(), ...).float()` bit for bit at half the bytes.  Served by the kernels built into the library (the general ones,
-        the Panda and Puma560 instantiations), not by run-time instantiations; not with base_wrench=True.  NumPy float32 is converted on the host."""
+        the Panda and Puma560 instantiations), not by run-time instantiations; not with base_wrench=True.  NumPy float32 is converted on the host.
+        A CUDA q, qd or qdd that requires grad (gradients enabled) makes tau differentiable with respect to all three -- all-revolute chains,
+        not with base_wrench=True: the same forward call, one launch of rtbhip_rne_vjp in the backward pass (rtbhip/autograd.py)."""
+        if self._wants_grad(q, qd, qdd) and not base_wrench:
+            from . import autograd
+            return autograd.differentiable_rne(self, q, qd, qdd, gravity, fext)
         if base_wrench:
             # robot/DHRobot.py:1409-1412 sends base_wrench=True to rne_python (:1458-1796), which returns (tau, wbase) with
             # wbase = [R_1 f_1, R_1 n_1] (:1765-1770): the wrench the base exerts on link 1 as the backward recursion holds it when it ends,
@@ -597,7 +606,11 @@ class DHRobot(RobotKinematics):
         (reference Dynamics.accel robot/Dynamics.py:424-509).  The solve is an LDL^T of the lower triangle of M as the recursion produces
         it.  One case where that matters: for a modified-DH chain whose FIRST joint is prismatic the reference's recursion (core/ne.c) yields a
         non-symmetric M (the first joint's force misses the link masses; `inertia` returns it as the reference does), and the reference's
-        accel solves with that full matrix -- the two answers differ there and neither is physical (tests/test_dropin_differential_cpu.py)."""
+        accel solves with that full matrix -- the two answers differ there and neither is physical (tests/test_dropin_differential_cpu.py).
+        Differentiable with respect to CUDA q, qd and torque that require grad (all-revolute chains, float64): rtbhip/autograd.py."""
+        if self._wants_grad(q, qd, torque):
+            from . import autograd
+            return autograd.differentiable_accel(self, q, qd, torque, gravity)
         arrs, N, single, tm, ptr, stream, mem, dev = self._dyn_args([q, qd, torque])
         gc = self._gravity_c(gravity)
         qdd = self._empty((N, self.n), tm, dev)
