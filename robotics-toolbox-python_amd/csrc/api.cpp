@@ -1159,10 +1159,15 @@ int rtbhip_partial_fkine0(rtbhip_chain_t chain, const double *q, int64_t N, cons
     if (c->n < 1) return refuse(fn, "chain has no joints");
     if (N > 0 && !out) return refuse(fn, "NULL output");
     if (N == 0) return RTBHIP_OK;
+    const int n = c->n;
+    // the kernels' 24-bit index arithmetic (partial_device.h) holds n^order columns and 6 n^(order-1) doubles of the largest lower tensor per
+    // configuration: refused here, before the output (805 MB per configuration for 16 joints at order 6) is staged and the lower orders are
+    // allocated and launched -- launch_partial keeps its own check
+    if ((int64_t)partial_size(n, order) / 6 >= (1 << 24) || (int64_t)partial_size(n, order - 1) >= (1 << 24))
+        return refuse(fn, "tensor too large (n^order must stay below 2^24)", RTBHIP_ELIMIT);
     DevChain ops;
     RTB_TRY(chain_device_ops(c, &ops, nullptr));
     Affine base = affine_from16(nullptr), tool = affine_from16(tool16);
-    const int n = c->n;
     Staged st(mem, stream);
     const double *dq = st.in(q, (size_t)N * c->q_width * 8);
     double *dout = st.out(out, (size_t)N * (size_t)partial_size(n, order) * 8);

@@ -27,6 +27,8 @@ class Ctx:
         self.c = self._keep[0]._handle()          # Panda: n = q_width = 7
         self.cw = self._keep[1]._handle()         # n = 2, q_width = 3
         self.c0 = self._keep[2]._handle()         # a chain of constants: n = 0
+        self._long = [rtbhip.ETS([ET.Rz() if j % 2 else ET.Ry() for j in range(n)]) for n in (15, 16, 32)]
+        self.c15, self.c16, self.c32 = (e._handle() for e in self._long)      # chains of 15, 16 and 32 joints
         self.d = self._keep[3]._dyn_handle()
         self.t = self._keep[4]._handle()
         self._buf = np.zeros(4096)
@@ -242,6 +244,11 @@ def _frames_partial_rows():
     add("nojoints+nullout", pf, lambda x: (x.c0, x.B, 4, None, 3, None, HOST, None))
     add("empty", pf, lambda x: (x.c, x.B, 0, None, 3, x.B, HOST, None))
     add("empty4", pf, lambda x: (x.c, None, 0, None, 4, None, DEV, None))
+    # n^order >= 2^24: refused by the entry point itself, before the output (far larger than x.B) is staged or touched
+    add("16joints-order6", pf, lambda x: (x.c16, x.B, 1, None, 6, x.B, HOST, None))
+    add("32joints-order5", pf, lambda x: (x.c32, x.B, 1, None, 5, x.B, HOST, None))
+    add("32joints-order5+nullout", pf, lambda x: (x.c32, x.B, 1, None, 5, None, HOST, None))
+    add("15joints-order6-empty", pf, lambda x: (x.c15, x.B, 0, None, 6, x.B, HOST, None))
     return rows
 
 
@@ -680,6 +687,10 @@ EXPECTED = {
     'partial_fkine0-nojoints+nullout': (EINVAL, 'partial_fkine0: chain has no joints'),
     'partial_fkine0-empty': (OK, None),
     'partial_fkine0-empty4': (OK, None),
+    'partial_fkine0-16joints-order6': (ELIMIT, 'partial_fkine0: tensor too large (n^order must stay below 2^24)'),
+    'partial_fkine0-32joints-order5': (ELIMIT, 'partial_fkine0: tensor too large (n^order must stay below 2^24)'),
+    'partial_fkine0-32joints-order5+nullout': (EINVAL, 'partial_fkine0: NULL output'),
+    'partial_fkine0-15joints-order6-empty': (OK, None),
     'ik_lm-unknown': (EINVAL, 'ik_lm: unknown chain handle'),
     'ik_lm-negN': (EINVAL, 'ik_lm: negative N'),
     'ik_lm-nullTep': (EINVAL, 'ik_lm: NULL input with N > 0'),
