@@ -370,6 +370,13 @@ int rtbhip_tree_destroy(rtbhip_tree_t tree);
 int rtbhip_tree_upload(rtbhip_tree_t tree, int32_t device); /* as rtbhip_chain_upload */
 int rtbhip_tree_rne(rtbhip_tree_t tree, const double *q, const double *qd, const double *qdd, int64_t N,
                     const double *gravity3, double *tau, int32_t mem, void *stream);
+/* The vector-Jacobian product of rtbhip_tree_rne: for the gradient gtau (N,ng) of a scalar loss with respect to the torques, the gradients
+ * gq, gqd, gqdd (N,ng each; NULL = not wanted, at least one required) with respect to q, qd and qdd.  q, qd, qdd and gravity3 are those of the
+ * forward call (qd and / or qdd NULL = zeros); gravity is a constant of the differentiation.  gtau is read by torque column (group order),
+ * q, qd, qdd and the gradients by q column (jindex).  Every joint kind the forward call serves: revolute, prismatic, flipped, branched trees.
+ * One fused kernel, one launch: trees of 1..8 groups in registers, 9..24 through a run-time-n kernel; RTBHIP_ELIMIT beyond 24 groups. */
+int rtbhip_tree_rne_vjp(rtbhip_tree_t tree, const double *q, const double *qd, const double *qdd, int64_t N, const double *gravity3,
+                        const double *gtau, double *gq, double *gqd, double *gqdd, int32_t mem, void *stream);
 
 /* The Dynamics-mixin terms of an ETS robot -- Dynamics.inertia / coriolis / accel (robot/Dynamics.py:704-763, 765-861, 424-509), which the
  * reference builds from n, n + n(n-1)/2 and n + 1 calls of Robot.rne per configuration -- one fused kernel each, every pass of a

@@ -648,6 +648,9 @@ __attribute__((weak)) int launch_rne_vjp(const Dyn *d, const DevLink *links, con
 __attribute__((weak)) int launch_rne_vjp_f32(const Dyn *d, const DevLink *links, const float *q, const float *qd, const float *qdd, int64_t N,
                                              const double *grav3, const double *fext6, const float *gtau, float *gq, float *gqd, float *gqdd,
                                              hipStream_t s);
+// ... and of the link-tree adjoint (tree_rne_vjp_kernels.hip), weak for the same reason
+__attribute__((weak)) int launch_tree_rne_vjp(const Tree *t, const DevGroup *groups, const double *q, const double *qd, const double *qdd, int64_t N,
+                                              const double *grav3, const double *gtau, double *gq, double *gqd, double *gqdd, hipStream_t s);
 namespace {
 
 // rtbhip_rne_vjp / rtbhip_rne_vjp_f32: the gradient of a loss on rtbhip_rne's torques with respect to q, qd and qdd (k_rne_vjp)
@@ -1335,6 +1338,32 @@ int rtbhip_tree_rne(rtbhip_tree_t tree, const double *q, const double *qd, const
     double *dtau = st.out(tau, bytes);
     RTB_TRY(st.status());
     return st.finish(launch_tree_rne(t, groups, dq, dqd, dqdd, N, gravity3, dtau, st.stream()));
+}
+
+// the gradient of a loss on rtbhip_tree_rne's torques with respect to q, qd and qdd (k_tree_rne_vjp)
+int rtbhip_tree_rne_vjp(rtbhip_tree_t tree, const double *q, const double *qd, const double *qdd, int64_t N, const double *gravity3,
+                        const double *gtau, double *gq, double *gqd, double *gqdd, int32_t mem, void *stream)
+{
+    const char *fn = "tree_rne_vjp";
+    const std::shared_ptr<Tree> t_owner = tree_from_handle(tree);
+    Tree *t = t_owner.get();
+    RTB_TRACE(fn);
+    if (!t) return refuse(fn, "unknown tree handle");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    if (N == 0) return RTBHIP_OK;                            // an empty batch: no pointer is looked at
+    if (!gtau) return refuse(fn, "NULL gtau");               // qd / qdd may be NULL (= zeros)
+    if (!gq && !gqd && !gqdd) return refuse(fn, "gq, gqd and gqdd are all NULL: there is nothing to compute");
+    if (!gravity3) return refuse(fn, "NULL gravity");        // (read on the host, as rtbhip_tree_rne's)
+    if (!launch_tree_rne_vjp) return refuse(fn, "not built into this library");
+    const DevGroup *groups = nullptr;
+    RTB_TRY(tree_device_groups(t, &groups));
+    const size_t bytes = (size_t)N * t->n * 8;
+    Staged st(mem, stream);
+    const double *dq = st.in(q, bytes), *dqd = st.in(qd, bytes), *dqdd = st.in(qdd, bytes), *dg = st.in(gtau, bytes);
+    double *dgq = st.out(gq, bytes), *dgqd = st.out(gqd, bytes), *dgqdd = st.out(gqdd, bytes);
+    RTB_TRY(st.status());
+    return st.finish(launch_tree_rne_vjp(t, groups, dq, dqd, dqdd, N, gravity3, dg, dgq, dgqd, dgqdd, st.stream()));
 }
 
 int rtbhip_inertia(rtbhip_dyn_t dyn, const double *q, int64_t N, double *M, int32_t mem, void *stream)

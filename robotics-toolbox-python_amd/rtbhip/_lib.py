@@ -60,6 +60,10 @@ class _sq(_sp):
     """`void *stream` of rtbhip_rne_vjp / rtbhip_rne_vjp_f32: as _sp, a type of its own; their refusal rows and census are in tests/test_rne_vjp.py."""
 
 
+class _st(_sq):
+    """`void *stream` of rtbhip_tree_rne_vjp: as _sp, a type of its own; its refusal rows and census are in tests/test_tree_rne_vjp.py."""
+
+
 # name -> (restype, argtypes); must list every symbol include/rtbhip.h declares
 SIGNATURES = {
     "rtbhip_last_error": (C.c_char_p, []),
@@ -117,6 +121,7 @@ SIGNATURES = {
     "rtbhip_tree_create": (C.c_int, [C.POINTER(rtbhip_tree_group), _i32, C.POINTER(_u64)]),
     "rtbhip_tree_destroy": (C.c_int, [_u64]),
     "rtbhip_tree_rne": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "rtbhip_tree_rne_vjp": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _st]),
     "rtbhip_tree_inertia": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp]),
     "rtbhip_tree_coriolis": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp]),
     "rtbhip_tree_accel": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),

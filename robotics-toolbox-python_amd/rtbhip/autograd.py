@@ -11,7 +11,11 @@ The dynamics (rtbhip/dh.py routes here for all-revolute DH chains, never with ba
 rtbhip_rne_vjp(_f32), which returns the gradients autograd asks for (ctx.needs_input_grad) and no others.  _AccelVJP needs no kernel of its
 own: with qdd = accel(q, qd, torque) and g its incoming gradient, lambda = M^-1 g is one more accel call (qd = 0, no gravity; M is symmetric for
 an all-revolute chain), the gradient of torque is lambda and those of q and qd are rne_vjp's at (q, qd, qdd) for gtau = -lambda (the implicit
-function theorem on  rne(q, qd, qdd) = torque).  inertia, coriolis, the ETS robots' dynamics: not differentiable, unchanged."""
+function theorem on  rne(q, qd, qdd) = torque).
+
+The dynamics of ETS / URDF robots (rtbhip/erobot.py routes here): _TreeRneVJP's backward is one launch of rtbhip_tree_rne_vjp -- every joint kind
+the forward kernel serves, float64 -- and _TreeAccelVJP is _AccelVJP's construction on it, for robots numbered in group order (M symmetric).
+inertia, coriolis: not differentiable, unchanged."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -134,3 +138,72 @@ def differentiable_rne(robot, q, qd, qdd, gravity, fext):
 def differentiable_accel(robot, q, qd, torque, gravity):
     """DHRobot.accel(q, qd, torque, gravity=) attached to the autograd graph of its inputs"""
     return _AccelVJP.apply(q, qd, torque, robot, gravity)
+
+
+# ---------------------------------------------------------------- the dynamics of an ETS / URDF robot (link tree)
+def _tree_rne_vjp(robot, q, qd, qdd, gtau, gravity, want):
+    """rtbhip_tree_rne_vjp on the current stream: the gradients named by `want` (three booleans), each shaped like its input; None for the others"""
+    import numpy as np
+    n = robot.n
+    rows = lambda x: None if x is None else x.detach().reshape(-1, n).contiguous()
+    q2, qd2, qdd2 = rows(q), rows(qd), rows(qdd)
+    g2 = gtau.detach().to(q2.dtype).reshape(-1, n).contiguous()
+    N = q2.shape[0]
+    outs = [torch.empty_like(q2) if w else None for w in want]
+    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    g = np.ascontiguousarray(robot.gravity if gravity is None else np.asarray(gravity, dtype=np.float64).reshape(3))
+    check(lib().rtbhip_tree_rne_vjp(robot._handle(), ptr(q2), ptr(qd2), ptr(qdd2), N, host_ptr(g), ptr(g2), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]),
+                                    MEM_DEVICE, current_stream_ptr()))
+    return [None if o is None else o.reshape(x.shape) for o, x in zip(outs, (q, qd, qdd))]
+
+
+class _TreeRneVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, qd, qdd, robot, gravity):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, qd, qdd)
+        ctx.robot, ctx.gravity = robot, gravity
+        return robot.rne(q, qd, qdd, gravity=gravity)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gtau):
+        q, qd, qdd = ctx.saved_tensors
+        want = [bool(w) for w in ctx.needs_input_grad[:3]]
+        if gtau is None or not any(want):
+            return None, None, None, None, None
+        gq, gqd, gqdd = _tree_rne_vjp(ctx.robot, q, qd, qdd, gtau, ctx.gravity, want)
+        return gq, gqd, gqdd, None, None
+
+
+class _TreeAccelVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, qd, torque, robot, gravity):
+        ctx.set_materialize_grads(False)
+        qdd = robot.accel(q, qd, torque, gravity=gravity)
+        ctx.save_for_backward(q, qd, qdd)
+        ctx.robot, ctx.gravity = robot, gravity
+        return qdd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        q, qd, qdd = ctx.saved_tensors
+        want = [bool(w) for w in ctx.needs_input_grad[:3]]
+        if g is None or not any(want):
+            return None, None, None, None, None
+        lam = ctx.robot.accel(q.detach(), torch.zeros_like(qd), g.to(q.dtype).reshape(q.shape).contiguous(), gravity=[0.0, 0.0, 0.0])       # M^-1 g
+        gq = gqd = None
+        if want[0] or want[1]:
+            gq, gqd, _ = _tree_rne_vjp(ctx.robot, q, qd, qdd, -lam, ctx.gravity, [want[0], want[1], False])
+        return gq, gqd, (lam.reshape(q.shape) if want[2] else None), None, None
+
+
+def differentiable_tree_rne(robot, q, qd, qdd, gravity):
+    """ERobot.rne(q, qd, qdd, gravity=) attached to the autograd graph of its tensor inputs (qd / qdd may be None)"""
+    return _TreeRneVJP.apply(q, qd, qdd, robot, gravity)
+
+
+def differentiable_tree_accel(robot, q, qd, torque, gravity):
+    """ERobot.accel(q, qd, torque, gravity=) attached to the autograd graph of its inputs (robots numbered in group order)"""
+    return _TreeAccelVJP.apply(q, qd, torque, robot, gravity)

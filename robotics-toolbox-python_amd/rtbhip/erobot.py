@@ -384,6 +384,10 @@ class ERobot(RobotKinematics):
                 cur = []
         return groups
 
+    def _in_group_order(self):
+        """group j moves q column j for every j: the numbering ERobot assigns by itself, and every URDF robot's"""
+        return all(int(self.links[idx[-1]].jindex) == g for g, idx in enumerate(self.link_groups()))
+
     def group_table(self):
         """One record per link group for rtbhip_tree_create (see include/rtbhip.h)."""
         groups = self.link_groups()
@@ -462,10 +466,15 @@ class ERobot(RobotKinematics):
             pass
 
     def rne(self, q, qd=None, qdd=None, symbolic=False, gravity=None):
-        """Inverse dynamics: (n,) or (N,n) (reference Robot.rne robot/Robot.py:1704-1903)."""
+        """Inverse dynamics: (n,) or (N,n) (reference Robot.rne robot/Robot.py:1704-1903).
+        A CUDA q, qd or qdd that requires grad (gradients enabled) makes tau differentiable with respect to all three, for every joint kind:
+        the same forward call, one launch of rtbhip_tree_rne_vjp in the backward pass (rtbhip/autograd.py)."""
         if symbolic:
             raise TypeError("Symbolic value")          # symbolic dynamics stay on the reference's Python path
         n = self.n
+        if n > 0 and any(_lib.wants_grad(x) for x in (q, qd, qdd)):
+            from . import autograd
+            return autograd.differentiable_tree_rne(self, q, qd, qdd, gravity)
         first = q
         tm = is_torch(first) and first.is_cuda
         if tm:
@@ -540,7 +549,12 @@ class ERobot(RobotKinematics):
         return Cm[0] if single else Cm
 
     def accel(self, q, qd, torque, gravity=None):
-        """Forward dynamics qdd = M(q)^-1 (torque - rne(q, qd, 0)): (n,) or (N,n) (reference Dynamics.accel robot/Dynamics.py:424-509)."""
+        """Forward dynamics qdd = M(q)^-1 (torque - rne(q, qd, 0)): (n,) or (N,n) (reference Dynamics.accel robot/Dynamics.py:424-509).
+        Differentiable with respect to CUDA q, qd and torque that require grad when the joints are numbered in group order (the default
+        numbering: M is symmetric there); a hand-numbered robot takes the ordinary path (rtbhip/autograd.py)."""
+        if self.n > 0 and any(_lib.wants_grad(x) for x in (q, qd, torque)) and self._in_group_order():
+            from . import autograd
+            return autograd.differentiable_tree_accel(self, q, qd, torque, gravity)
         arrs, N, single, ptr, stream, mem, empty = self._dyn_args([q, qd, torque])
         g = np.ascontiguousarray(self.gravity if gravity is None else np.asarray(gravity, dtype=np.float64).reshape(3))
         qdd = empty((N, self.n))
