@@ -111,8 +111,9 @@ __global__ __launch_bounds__(kWave) void k_kin_f32(KinParams kp, DevChain dc, co
 #define RTB_REG_WAVES 3   // waves per SIMD the register allocator must leave room for (<= 168 VGPRs)
 #endif
 // One register-resident tile (64 configurations) of a chain with NJ joints; shared by k_kin_reg and k_fleet.
+// (its rounds' row counts and widths are compile-time numbers: a full round takes the unrolled flush, kin_tile.h: flush_full)
 // SIG != 0: the chain's structure signature (kin_reg.h) -- the walk is straight-line code specialised for the robot's constants (k_fleet: always 0)
-template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false, SegSig SIG = 0, class S>
+template <int NJ, bool WANT_T, bool WANT_J, bool PACKED = false, SegSig SIG = 0, int PIPE = 1, class S>
 __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &cv, const S *__restrict__ q,
                                          S *__restrict__ T, S *__restrict__ J, double *buf, int lane,
                                          int64_t tile)
@@ -134,7 +135,7 @@ __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &
             __syncthreads();
             int rows = ncfg - r * kPRound;
             rows = rows < 0 ? 0 : (rows > kPRound ? kPRound : rows);
-            kin_flush_packed(bufT, bufJ, W + 1, W, rows, T + (cfg0 + r * kPRound) * (16 + W), lane);
+            kin_flush_packed<true, PIPE * kPRound, W>(bufT, bufJ, W + 1, W, rows, T + (cfg0 + r * kPRound) * (16 + W), lane);
             __syncthreads();
         }
         return;
@@ -142,8 +143,8 @@ __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &
     if (WANT_T) {
         reg_stage_T(kp, P, buf, lane);
         __syncthreads();
-        if (kp.pad & kKinPosePlain) kin_flush<false>(buf, 17, 16, ncfg, T + cfg0 * 16, lane);      // wave-uniform
-        else kin_flush<true>(buf, 17, 16, ncfg, T + cfg0 * 16, lane);
+        if (kp.pad & kKinPosePlain) kin_flush<false, PIPE * kWave, 16>(buf, 17, 16, ncfg, T + cfg0 * 16, lane);      // wave-uniform
+        else kin_flush<true, PIPE * kWave, 16>(buf, 17, 16, ncfg, T + cfg0 * 16, lane);
         __syncthreads();
     }
     if (WANT_J) {
@@ -153,7 +154,7 @@ __device__ __forceinline__ void reg_tile(const KinParams &kp, const ConstChain &
             __syncthreads();
             int rows = ncfg - r * kJRound;
             rows = rows < 0 ? 0 : (rows > kJRound ? kJRound : rows);
-            kin_flush(buf, W + 1, W, rows, J + (cfg0 + r * kJRound) * W, lane);
+            kin_flush<true, PIPE * kJRound, W>(buf, W + 1, W, rows, J + (cfg0 + r * kJRound) * W, lane);
             __syncthreads();
         }
     }
@@ -824,19 +825,20 @@ __global__ __launch_bounds__(kWave, (CLS == 0 ? RTB_REG_WAVES : 2)) void k_fleet
     const int64_t local = gt - fe.tile0, ctiles = (fe.N + kWave - 1) / kWave;
     const int64_t tile = (ctiles <= 0x7fffffff) ? (int64_t)xcd_tile_of((unsigned)ctiles, (unsigned)local) : local;
     if (CLS == 0) {
+        // (PIPE = 0: the unrolled flush in all ten tiles of this kernel cost it up to 28 VGPRs -- 165 -> 193, a wave per SIMD; it keeps the rolled one)
         switch (fe.n) {
-        case 1: reg_tile<1, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
-        case 2: reg_tile<2, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
-        case 3: reg_tile<3, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
-        case 4: reg_tile<4, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
-        case 5: reg_tile<5, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
-        case 6: reg_tile<6, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
-        case 7: reg_tile<7, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
-        default: reg_tile<8, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
+        case 1: reg_tile<1, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
+        case 2: reg_tile<2, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
+        case 3: reg_tile<3, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
+        case 4: reg_tile<4, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
+        case 5: reg_tile<5, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
+        case 6: reg_tile<6, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
+        case 7: reg_tile<7, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
+        default: reg_tile<8, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile); return;
         }
     } else if (CLS == 1) {
-        if (fe.n == 9) reg_tile<9, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile);
-        else reg_tile<10, true, true, PACKED>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile);
+        if (fe.n == 9) reg_tile<9, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile);
+        else reg_tile<10, true, true, PACKED, 0, 0>(kp, ops, fe.q, fe.T, fe.J, lds, lane, tile);
         return;
     }
     double *rows = lds;

@@ -104,12 +104,13 @@ RTB_HD void reg_walk_step(const CV &cv, Pose &P, double (&jac)[6 * NJ], const in
         if (SIG == 0) sched_fence();          // (signature kernels: no fence -- visit k: 0.8337 -> 0.8302 ms, every second one 0.8337)
     }
 }
-template <int NJ, bool WANT_J, bool PLAIN, SegSig SIG, int J = 0, class CV>
+// joints J .. JEND - 1
+template <int NJ, bool WANT_J, bool PLAIN, SegSig SIG, int J = 0, int JEND = NJ, class CV>
 RTB_HD void reg_walk_steps(const CV &cv, Pose &P, double (&jac)[6 * NJ], const int (&jmv)[NJ], const double (&c)[NJ], const double (&s)[NJ], const double (&d)[NJ])
 {
-    if constexpr (J < NJ) {
+    if constexpr (J < JEND) {
         reg_walk_step<NJ, WANT_J, PLAIN, SIG, J>(cv, P, jac, jmv, c, s, d);
-        reg_walk_steps<NJ, WANT_J, PLAIN, SIG, J + 1>(cv, P, jac, jmv, c, s, d);
+        reg_walk_steps<NJ, WANT_J, PLAIN, SIG, J + 1, JEND>(cv, P, jac, jmv, c, s, d);
     }
 }
 
@@ -149,6 +150,104 @@ RTB_HD void reg_close_jacobian(const Pose &P, int frame, const int (&jmv)[NJ], d
     }
 }
 
+// The constants a structure signature's walk reads, as VALUES: C_0 whole (pose_from_seg), of every later segment the rotation entries its class
+// leaves general and the non-zero components of its translation (pose_mul_seg_sig: the others are never read) -- 12 + 26 doubles for the Panda ETS.
+// Read from the table segment by segment inside the walk, each group of scalar loads was waited for where it was issued: nine round trips in
+// series, which the first wave of a launch on a CU has nobody to hide behind.  Instead:
+//   sig_touch   (reg_compute, behind the q loads) one word of every 64-byte line of the table: the lines are in the scalar cache by the time the
+//               sines are done -- the words themselves are waited for together with the q values and dropped;
+//   sig_fetch   (reg_core, behind the library-sincos branch, so nothing is parked across it) the constants in TWO clauses with one wait each: the
+//               segments before sig_split at the head of the walk, the others two products before the first of them is used -- all at once they
+//               overflow the scalar registers (the Panda's 76 beside the base transform's 24: 116 spilled, 320 bytes of scratch).  The walk then
+//               finds them in registers.  A chain with more than kSigFetchMax such constants (the UR arms: 65) keeps the table's view and has the
+//               touch alone.
+// SigSegs is a view like the table's own (seg[j].r / .t), without the traits of the fused views: both steps are for the unfused views only (k_kin_reg);
+// k_ik's and k_kin_diff's walks are not touched.
+template <int NJ>
+struct SigSegs {
+    DevSeg seg[NJ + 1];
+    const int32_t *jmeta;      // (a signature's walk is PLAIN: never read)
+};
+constexpr bool sig_reads_entry(SegSig sig, int j, int k /* 0..8: r[k], 9..11: t[k - 9] */)
+{
+    const int cls = seg_sig_cls(sig, j), tm = seg_sig_tm(sig, j);
+    if (j == 0 || cls == kSegGeneral || ((RTB_SIG_UNFUSED_GENERAL >> cls) & 1)) return true;
+    return k < 9 ? seg_kind(cls, k) == kCA : ((tm >> (k - 9)) & 1) != 0;
+}
+constexpr int sig_reads_count(SegSig sig, int j0, int j1, int k1 = 0)      // entries read of segments j0 .. j1 - 1, and of the first k1 of segment j1
+{
+    int m = 0;
+    for (int a = j0; a <= j1; ++a)
+        for (int b = 0; b < (a < j1 ? 12 : k1); ++b) m += sig_reads_entry(sig, a, b) ? 1 : 0;
+    return m;
+}
+constexpr int kSigFetchMax = 40;      // doubles in the two clauses together (each is pinned by one statement of at most 30 operands)
+constexpr int sig_split(SegSig sig, int nj)      // first segment of the second clause: the first clause holds at least half
+{
+    int h = 1;
+    while (h <= nj && 2 * sig_reads_count(sig, 0, h) < sig_reads_count(sig, 0, nj + 1)) ++h;
+    return h;
+}
+constexpr bool sig_fetches(SegSig sig, int nj)
+{
+    if (sig == 0 || nj > 8) return false;
+    const int h = sig_split(sig, nj);
+    return sig_reads_count(sig, 0, nj + 1) <= kSigFetchMax && sig_reads_count(sig, 0, h) <= 30 && sig_reads_count(sig, h, nj + 1) <= 30;
+}
+// f(IntC<j>, IntC<k>, IntC<slot>) for every entry the walk reads of segments J0 .. J1 - 1, slot = 0, 1, ... in table order: all three are
+// compile-time numbers in f (a loop's would be constants only after unrolling, and the slot arithmetic did not fold: the values went to scratch)
+template <int V> struct IntC { static constexpr int v = V; };
+template <SegSig SIG, int J0, int J1, int I = 12 * J0, class F>
+RTB_HD void sig_each(F f)
+{
+    if constexpr (I < 12 * J1) {
+        if constexpr (sig_reads_entry(SIG, I / 12, I % 12)) f(IntC<I / 12>(), IntC<I % 12>(), IntC<sig_reads_count(SIG, J0, I / 12, I % 12)>());
+        sig_each<SIG, J0, J1, I + 1>(f);
+    }
+}
+// segments J0 .. J1 - 1 of the table into the view (the entries nothing reads stay as they are)
+template <SegSig SIG, int NJ, int J0, int J1, class CV>
+RTB_HD void sig_fetch(const CV &cv, SigSegs<NJ> &cs)
+{
+    static_assert(!cv_fused_translation<CV>::value, "the unfused views' reading pattern");
+    sig_each<SIG, J0, J1>([&](auto j, auto k, auto) {
+        if constexpr (k.v < 9) cs.seg[j.v].r[k.v] = cv.seg[j.v].r[k.v];
+        else cs.seg[j.v].t[k.v - 9] = cv.seg[j.v].t[k.v - 9];
+    });
+#if defined(__HIP_DEVICE_COMPILE__)
+    // All of them live in scalar registers HERE, or the loads are handed out along the walk again, one by one with a wait each.  ONE statement takes
+    // them all as operands (the last one again in the unused places), because a load is placed in front of the first statement that needs it: a
+    // statement per value put most of the loads, and a wait each, between the statements.  The fences keep the walk's arithmetic from moving up
+    // past it, which would come to the same.
+    constexpr int m = sig_reads_count(SIG, J0, J1);
+    static_assert(m >= 1 && m <= 30, "one statement's operands");
+    double v[m];
+    sig_each<SIG, J0, J1>([&](auto j, auto k, auto slot) {
+        if constexpr (k.v < 9) v[slot.v] = cs.seg[j.v].r[k.v];
+        else v[slot.v] = cs.seg[j.v].t[k.v - 9];
+    });
+#define RTB_PIN(i) "s"(v[(i) < m ? (i) : m - 1])
+    sched_fence();
+    asm volatile("" ::RTB_PIN(0), RTB_PIN(1), RTB_PIN(2), RTB_PIN(3), RTB_PIN(4), RTB_PIN(5), RTB_PIN(6), RTB_PIN(7), RTB_PIN(8), RTB_PIN(9), RTB_PIN(10),
+                 RTB_PIN(11), RTB_PIN(12), RTB_PIN(13), RTB_PIN(14), RTB_PIN(15), RTB_PIN(16), RTB_PIN(17), RTB_PIN(18), RTB_PIN(19), RTB_PIN(20),
+                 RTB_PIN(21), RTB_PIN(22), RTB_PIN(23), RTB_PIN(24), RTB_PIN(25), RTB_PIN(26), RTB_PIN(27), RTB_PIN(28), RTB_PIN(29));
+    sched_fence();
+#undef RTB_PIN
+#endif
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+// one word of each 64-byte line of the NJ + 1 segments (the table starts a device allocation: line-aligned); nothing past the table is read
+template <int NJ, class CV>
+__device__ __forceinline__ void sig_touch(const CV &cv)
+{
+    const auto *w = (const __attribute__((address_space(4))) int32_t *)cv.seg;
+    int any = 0;
+#pragma unroll
+    for (int b = 0; b < (NJ + 1) * (int)sizeof(DevSeg); b += 64) any |= w[b / 4];
+    asm volatile("" ::"s"(any));
+}
+#endif
+
 // PLAIN (compile-time): every joint is revolute and none is flipped (the caller checked the chain's descriptors): no descriptor is read, no
 // wave-uniform branch splits the walk -- one straight-line block from the first sine to the last Jacobian column.
 template <int NJ, bool WANT_J, bool PLAIN = false, SegSig SIG = 0, class CV, class TL>
@@ -179,6 +278,18 @@ RTB_HD void reg_core(const CV &cv, TL tail /* tail[k], k = 0..11 */, int frame, 
 #pragma unroll
         for (int j = 0; j < NJ; ++j) sincos(d[j], &s[j], &c[j]);
     }
+    if constexpr (sig_fetches(SIG, NJ) && !cv_fused_translation<CV>::value) {      // k_kin_reg's signature walk: its constants in two clauses (sig_fetch)
+        constexpr int H = sig_split(SIG, NJ), E = H >= 2 ? H - 2 : 0;      // joint E's product is the second before segment H's
+        SigSegs<NJ> cs = {};
+        sig_fetch<SIG, NJ, 0, H>(cv, cs);
+        reg_walk_steps<NJ, WANT_J, PLAIN, SIG, 0, E>(cs, P, jac, jmv, c, s, d);
+        if constexpr (H <= NJ) sig_fetch<SIG, NJ, H, NJ + 1>(cv, cs);
+        reg_walk_steps<NJ, WANT_J, PLAIN, SIG, E, NJ>(cs, P, jac, jmv, c, s, d);
+        pose_mul_seg_by_sig<SIG, NJ>(P, cs);
+        sched_fence();
+        reg_close_jacobian<NJ, WANT_J>(P, frame, jmv, jac);
+        return;
+    }
     reg_walk_steps<NJ, WANT_J, PLAIN, SIG>(cv, P, jac, jmv, c, s, d);
     // k_ik's chain views: the tail IS segment NJ of the table (no tool in IK), descriptor NJ carries its class
     if constexpr (SIG != 0) pose_mul_seg_by_sig<SIG, NJ>(P, cv);
@@ -200,12 +311,17 @@ RTB_HD void reg_compute(const KinParams &kp, const CV &cv, const S *__restrict__
     if constexpr (SIG != 0) {
         // the launch's ramp is this kernel's to shorten: the NJ column words first, then NJ loads with nothing between them -- a dead lane reads
         // row 0 (N >= 1) instead of branching round its load, which put a scalar load, its wait and a branch in front of every q load
+        // (the column words passed in the kernarg instead, so that the q loads wait for one scalar round trip, were not shown to gain -- nothing at a
+        // resident round, one wave inside its process-to-process scatter -- and are not in: profiles/r08_kin_wave_latency.txt)
         const S *qrow = q + (live ? cfg : 0) * kp.qw;
         int jq[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) jq[j] = jm_jq(cv.jmeta[j]);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) qv[j] = qrow[jq[j]];
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (!cv_fused_translation<CV>::value) sig_touch<NJ>(cv);      // the table's lines, on their way while the q values are (sig_fetch, above)
+#endif
 #pragma unroll
         for (int j = 0; j < NJ; ++j) qv[j] = live ? qv[j] : 0.0;
         reg_core<NJ, WANT_J, true, SIG>(cv, &cv.seg[NJ].r[0], kp.frame, qv, P, jac);

@@ -102,13 +102,72 @@ RTB_HD void store_pair_f32(float *__restrict__ dst, double a, double b)
 #endif
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// A FULL round of a flush whose row count and row width are compile-time numbers (the register-resident tile: kin_kernels.hip, reg_tile): the
+// run's length is then a constant, a lane's pieces are unrolled, and the LDS reads run kFlushGroup pieces ahead of the stores -- each store waits
+// by count for its own pair only, and the read of piece p + kFlushGroup is issued behind it.  In the rolled loop below every piece waited for its own LDS round trip: 29 in series
+// per lane for the Panda's T + J, which shows where a wave has nobody to hide behind (the first and the last waves of a launch).
+// Same pieces, same lanes, same addresses as the loop: piece p of lane l is the pair at f = 2 l + 128 p, present while f < total (total is even).
+// src_of(f) -> the pair's place in LDS.
+constexpr int kFlushGroup = 3;      // (4 cost the float32 T+J signature kernel its fourth wave: 129 VGPRs)
+template <bool NT, class S>
+__device__ __forceinline__ void store_piece(S *__restrict__ dst, double a, double b)
+{
+    if constexpr (sizeof(S) == 4) {
+        store_pair_f32<NT>(dst, a, b);
+    } else {
+        typedef double v2d __attribute__((ext_vector_type(2)));
+        v2d w = {a, b};
+        if (NT) __builtin_nontemporal_store(w, reinterpret_cast<v2d *>(dst));   // global_store_dwordx4 ... nt
+        else *reinterpret_cast<v2d *>(dst) = w;
+    }
+}
+template <bool NT, int TOTAL, class S, class Src>
+__device__ __forceinline__ void flush_full(S *__restrict__ dst, int lane, Src src_of)
+{
+    static_assert(TOTAL > 0 && TOTAL % 2 == 0, "whole pairs");
+    constexpr int NP = (TOTAL + 127) / 128;
+    double a[kFlushGroup], b[kFlushGroup];      // slot p % kFlushGroup holds piece p between its read and its store
+    // A caller that picks the store kind by a wave-uniform flag (reg_tile's pose flush) has this body twice, the same but for the `nt` of its stores:
+    // the optimiser folded the two into one and dropped the flag -- every full pose tile went out with ordinary stores.  The markers (no
+    // instruction) at both ends of the non-temporal copy keep the two apart; the code object is checked for it (profiles/r08_kin_wave_latency.txt).
+    if (NT) asm volatile("");
+    auto has = [&](int p) { return 128 * (p + 1) <= TOTAL || 2 * lane + 128 * p < TOTAL; };      // (a whole piece: decided at compile time)
+    auto read = [&](int p) {
+        if (has(p)) {
+            const double *src = src_of(2 * lane + 128 * p);
+            a[p % kFlushGroup] = src[0];
+            b[p % kFlushGroup] = src[1];
+        }
+    };
+#pragma unroll
+    for (int p = 0; p < kFlushGroup && p < NP; ++p) read(p);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        if (has(p)) store_piece<NT>(dst + 2 * lane + 128 * p, a[p % kFlushGroup], b[p % kFlushGroup]);
+        if (p + kFlushGroup < NP) read(p + kFlushGroup);      // the slot is free again: kFlushGroup reads stay in flight ahead of the stores
+    }
+    if (NT) asm volatile("");
+}
+#endif
+
 // phases C / E: the wave writes `ncfg` staged rows of W doubles (W even) as one contiguous run.
 // Lane l writes the 16-byte pieces l, l+64, l+128, ... of the run; (cfg, e) tracks which staged
 // row / element piece f falls in without a division per piece.
-template <bool NT = true, class S>
+// FULL_ROWS, FULL_W (device code; 0: none): when the caller's rounds hold FULL_ROWS rows of FULL_W doubles and this one is full (ncfg == FULL_ROWS,
+// wave-uniform) it takes the unrolled form above; a ragged round -- the last tile of a batch -- and every caller with a run-time width take the loop.
+template <bool NT = true, int FULL_ROWS = 0, int FULL_W = 0, class S>
 RTB_HD void kin_flush(const double *rows, int stride, int W, int ncfg, S *__restrict__ dst,
                       int lane)
 {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (FULL_ROWS > 0) {
+        if (ncfg == FULL_ROWS) {
+            flush_full<NT, FULL_ROWS * FULL_W>(dst, lane, [&](int f) { const int cfg = (unsigned)f / (unsigned)FULL_W; return rows + cfg * stride + (f - cfg * FULL_W); });
+            return;
+        }
+    }
+#endif
     const int total = ncfg * W;
     int f = 2 * lane;
     int cfg = f / W, e = f - cfg * W;
@@ -145,9 +204,21 @@ RTB_HD void kin_flush(const double *rows, int stride, int W, int ncfg, S *__rest
 // PACKED output (SURVEY 8e's gather message: one (N, 16 + 6n) array, row = [T row-major 4x4 | J (6,n) C-order]): the wave writes `ncfg` staged
 // rows of 16 + W doubles as ONE contiguous run -- a single write stream per launch, where the two-array form has two.  T and J are staged in
 // separate LDS areas (rowsT: 17-double rows; rowsJ: `strideJ`-double rows); 16 and W are even, so a 16-byte piece never straddles the two.
-template <bool NT = true, class S>
+// (FULL_ROWS, FULL_W: as kin_flush -- FULL_W is the J part's width)
+template <bool NT = true, int FULL_ROWS = 0, int FULL_W = 0, class S>
 RTB_HD void kin_flush_packed(const double *rowsT, const double *rowsJ, int strideJ, int W, int ncfg, S *__restrict__ dst, int lane)
 {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (FULL_ROWS > 0) {
+        if (ncfg == FULL_ROWS) {
+            flush_full<NT, FULL_ROWS * (16 + FULL_W)>(dst, lane, [&](int f) {
+                const int cfg = (unsigned)f / (unsigned)(16 + FULL_W), e = f - cfg * (16 + FULL_W);
+                return e < 16 ? rowsT + cfg * 17 + e : rowsJ + cfg * strideJ + (e - 16);
+            });
+            return;
+        }
+    }
+#endif
     const int PW = 16 + W;
     const int total = ncfg * PW;
     int f = 2 * lane;
