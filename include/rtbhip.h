@@ -228,6 +228,13 @@ int rtbhip_jacobm(rtbhip_chain_t chain, const double *q, int64_t N, const double
  * makes frame m the product  base * E_1(q) ... E_k(q)  of the first k elementary transforms; out is (N, nmarks, 4, 4). */
 int rtbhip_link_frames(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16, const int32_t *marks,
                        int32_t nmarks, double *out, int32_t mem, void *stream);
+/* VECTOR-JACOBIAN PRODUCT of rtbhip_link_frames -- the backward pass of a loss on every frame at once, in one launch; no reference counterpart.
+ * gF (N, nmarks, 4, 4) is the loss's gradient with respect to the frames (the bottom row of each 4x4 is never read); gq (N, q_width):
+ * gq[i,c] = sum_m sum gF[i,m] dT_m[i]/dq_c, a column no joint of the chain reads is written as zero.  base16 and marks (HOST pointers, as there)
+ * are those of the forward call and are checked the same way.  nmarks == 0 with N > 0 writes zeros.  Chains of 1..32 joints, float64 rows;
+ * RTBHIP_EINVAL for a chain without joints. */
+int rtbhip_link_frames_vjp(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16, const int32_t *marks, int32_t nmarks,
+                           const double *gF, double *gq, int32_t mem, void *stream);
 
 /* ETS.partial_fkine0 (robot/ETS.py:1821-2013; Robot.partial_fkine0, robot/RobotKinematics.py:456-500): the
  * order-th partial derivative of the forward kinematics, order 3..6 (order 1 is jacob0, order 2 hessian0).

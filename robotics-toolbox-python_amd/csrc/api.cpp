@@ -651,6 +651,9 @@ __attribute__((weak)) int launch_rne_vjp_f32(const Dyn *d, const DevLink *links,
 // ... and of the link-tree adjoint (tree_rne_vjp_kernels.hip), weak for the same reason
 __attribute__((weak)) int launch_tree_rne_vjp(const Tree *t, const DevGroup *groups, const double *q, const double *qd, const double *qdd, int64_t N,
                                               const double *grav3, const double *gtau, double *gq, double *gqd, double *gqdd, hipStream_t s);
+// ... and of the all-frame adjoint of link_frames (frames_vjp_kernels.hip), weak for the same reason
+__attribute__((weak)) int launch_frames_vjp(const Chain *c, const DevChain &dc, const FrameTable &ft, const double *q, int64_t N, const double *gF,
+                                            double *gq, hipStream_t s);
 namespace {
 
 // rtbhip_rne_vjp / rtbhip_rne_vjp_f32: the gradient of a loss on rtbhip_rne's torques with respect to q, qd and qdd (k_rne_vjp)
@@ -1145,6 +1148,48 @@ int rtbhip_link_frames(rtbhip_chain_t chain, const double *q, int64_t N, const d
     double *dout = st.out(out, (size_t)N * nmarks * 128);
     RTB_TRY(st.status());
     return st.finish(launch_frames(c, ops, ft, dq, N, dout, st.stream()));
+}
+
+/* the gradient of a loss on rtbhip_link_frames' poses with respect to q (k_frames_vjp): every frame in one launch */
+int rtbhip_link_frames_vjp(rtbhip_chain_t chain, const double *q, int64_t N, const double *base16, const int32_t *marks, int32_t nmarks,
+                           const double *gF, double *gq, int32_t mem, void *stream)
+{
+    const char *fn = "link_frames_vjp";
+    const std::shared_ptr<Chain> c_owner = chain_from_handle(chain);
+    Chain *c = c_owner.get();
+    RTB_TRACE(fn);
+    if (!c) return refuse(fn, "unknown chain handle");
+    RTB_TRY(check_mem(fn, mem));
+    if (N < 0) return refuse(fn, "negative N");
+    if (nmarks > 0 && !marks) return refuse(fn, "NULL marks");
+    if (N > 0 && (!q || (nmarks > 0 && !gF))) return refuse(fn, "NULL input with N > 0");
+    if (N > 0 && !gq) return refuse(fn, "NULL gq");
+    if (c->n < 1) return refuse(fn, "chain has no joints");
+    FrameTable ft;
+    if (int rc = compile_frames(c, marks, nmarks, &ft)) {      // the lowering of rtbhip_link_frames, and its verdicts under this call's name
+        if (g_err.compare(0, 13, "link_frames: ") == 0) g_err = std::string(fn) + g_err.substr(11);
+        return rc;
+    }
+    if (N == 0) return RTBHIP_OK;
+    DeviceScope dscope;
+    if (mem == RTBHIP_MEM_DEVICE) RTB_TRY(dscope.enter_for(fn, q));
+    const size_t qbytes = (size_t)N * c->q_width * 8;
+    if (nmarks == 0) {                                         // no frame, no dependence on q: zeros
+        if (mem == RTBHIP_MEM_HOST) std::memset(gq, 0, qbytes);
+        else RTB_HIP(hipMemsetAsync(gq, 0, qbytes, (hipStream_t)stream));
+        return RTBHIP_OK;
+    }
+    if (!launch_frames_vjp) return refuse(fn, "not built into this library");
+    Staged st(mem, stream);
+    Affine b = affine_from16(base16);
+    ft.has_base = b.used;
+    for (int i = 0; i < 12; i++) ft.base[i] = b.v[i];
+    DevChain ops;
+    RTB_TRY(chain_device_ops(c, &ops, nullptr));
+    const double *dq = st.in(q, qbytes), *dgF = st.in(gF, (size_t)N * nmarks * 128);
+    double *dgq = st.out(gq, qbytes);
+    RTB_TRY(st.status());
+    return st.finish(launch_frames_vjp(c, ops, ft, dq, N, dgF, dgq, st.stream()));
 }
 
 /* ETS.partial_fkine0 (robot/ETS.py:1821-2013): order >= 3; orders 1 and 2 are jacob0 / hessian0 */

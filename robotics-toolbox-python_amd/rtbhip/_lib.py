@@ -64,6 +64,10 @@ class _st(_sq):
     """`void *stream` of rtbhip_tree_rne_vjp: as _sp, a type of its own; its refusal rows and census are in tests/test_tree_rne_vjp.py."""
 
 
+class _sf(_st):
+    """`void *stream` of rtbhip_link_frames_vjp: as _sp, a type of its own; its refusal rows and census are in tests/test_link_frames_vjp.py."""
+
+
 # name -> (restype, argtypes); must list every symbol include/rtbhip.h declares
 SIGNATURES = {
     "rtbhip_last_error": (C.c_char_p, []),
@@ -117,6 +121,7 @@ SIGNATURES = {
     "rtbhip_manipulability": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _vp]),
     "rtbhip_jacobm": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_link_frames": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "rtbhip_link_frames_vjp": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _sf]),
     "rtbhip_partial_fkine0": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp, _i32, _vp]),
     "rtbhip_tree_create": (C.c_int, [C.POINTER(rtbhip_tree_group), _i32, C.POINTER(_u64)]),
     "rtbhip_tree_destroy": (C.c_int, [_u64]),

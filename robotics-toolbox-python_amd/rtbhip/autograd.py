@@ -7,6 +7,9 @@ front end takes the path it always took), its backward one launch of rtbhip_fkin
 both outputs hang off one node, so a loss on T and J costs one backward launch.  The backward is not itself differentiable (no double
 backward).  Not differentiable at all, and unchanged: jacobe, frame=1, packed=True, out=, hessian0, the IK solvers.
 
+Every link frame (rtbhip/et.py routes ETS.link_frames here, and with it the fkine_all of every robot class): _FramesVJP's backward is one launch of
+rtbhip_link_frames_vjp for all the frames of the walk, float64.
+
 The dynamics (rtbhip/dh.py routes here for all-revolute DH chains, never with base_wrench=True): _RneVJP's backward is one launch of
 rtbhip_rne_vjp(_f32), which returns the gradients autograd asks for (ctx.needs_input_grad) and no others.  _AccelVJP needs no kernel of its
 own: with qdd = accel(q, qd, torque) and g its incoming gradient, lambda = M^-1 g is one more accel call (qd = 0, no gravity; M is symmetric for
@@ -69,6 +72,41 @@ def differentiable(ets, what, q, base, tool):
         with torch.no_grad():
             return _ordinary(ets, what, q, base, tool)
     return _KinVJP.apply(q, ets, what, small(base, 16), small(tool, 16))
+
+
+# ---------------------------------------------------------------- every link frame of a chain (ETS.link_frames, fkine_all)
+class _FramesVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, ets, marks, base):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q)
+        ctx.ets, ctx.marks, ctx.base = ets, marks, base
+        return ets.link_frames(q, marks, base=base)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gF):
+        (q,) = ctx.saved_tensors
+        if gF is None:
+            return None, None, None, None
+        ets, marks = ctx.ets, ctx.marks
+        q2, single, _ = ets._shape_q(q.detach())                       # the rows the forward read: (N, q_width), contiguous
+        N = q2.shape[0]
+        gF = gF.to(q2.dtype).reshape(N, len(marks), 16).contiguous()   # (a .sum() loss delivers a stride-0 expanded tensor)
+        gq = torch.empty_like(q2)
+        check(lib().rtbhip_link_frames_vjp(ets._handle(), C.c_void_p(q2.data_ptr()), N, host_ptr(ctx.base), host_ptr(marks), len(marks),
+                                           C.c_void_p(gF.data_ptr()), C.c_void_p(gq.data_ptr()), MEM_DEVICE, current_stream_ptr()))
+        if tuple(q.shape) != tuple(gq.shape):                          # q was one configuration, or rows wider than the chain reads
+            full = torch.zeros(q.shape, dtype=q.dtype, device=q.device)
+            (full.reshape(1, -1) if single else full)[:, :q2.shape[1]] = gq
+            gq = full
+        return gq, None, None, None
+
+
+def differentiable_link_frames(ets, q, marks, base):
+    """ETS.link_frames(q, marks, base=) attached to the autograd graph of q: the backward pass is one launch of rtbhip_link_frames_vjp for all frames"""
+    import numpy as np
+    return _FramesVJP.apply(q, ets, np.ascontiguousarray(marks, dtype=np.int32).reshape(-1), small(base, 16))
 
 
 # ---------------------------------------------------------------- the dynamics of a DH robot

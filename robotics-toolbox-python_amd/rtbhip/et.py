@@ -772,7 +772,11 @@ class ETS:
     def link_frames(self, q, marks, base=None):
         """Poses of intermediate frames: frame m = base * (product of the first marks[m] transforms).  (nmarks,4,4) for
         one q, (N,nmarks,4,4) for a trajectory -- what DHRobot.fkine_all / Robot.fkine_all build link by link in Python
-        (robot/DHRobot.py:1012-1064, robot/Robot.py:638-698), in one chain walk per configuration."""
+        (robot/DHRobot.py:1012-1064, robot/Robot.py:638-698), in one chain walk per configuration.
+        A CUDA q with requires_grad (and gradients enabled) gives frames that back-propagate to q: one launch for all of them (rtbhip/autograd.py)."""
+        if _lib.wants_grad(q) and self.n > 0:
+            from .autograd import differentiable_link_frames
+            return differentiable_link_frames(self, q, marks, base)
         marks = np.ascontiguousarray(marks, dtype=np.int32).reshape(-1)
         q2, single, tm = self._shape_q(q)
         N = q2.shape[0]
