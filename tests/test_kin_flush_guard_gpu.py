@@ -25,15 +25,13 @@ import pytest
 import rtbhip
 from rtbhip import urdf, _lib
 from helpers import replaying, chain_from_ets, product_ets
+from flush_guard import Guarded
 from oracle import oracle, chains
 
 # raw device pointers into guarded buffers, and two device kernels compared: not served by the CPU replay of the GPU suite
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(replaying(), reason="raw device pointers into guarded buffers: not served by the CPU replay")]
 
 SIZES = (1, 31, 32, 33, 63, 64, 65, 96, 127, 129, 200)
-GUARD = 64
-NAN64 = 0x7FF8DEAD0000BEEF
-NAN32 = 0x7FC0BEEF
 FORMS = ("T+J f0", "T+J f1", "packed f0", "packed f1", "T", "J f0", "J f1")
 
 
@@ -84,28 +82,6 @@ def _case(name):
 def _knob():
     yield
     rtbhip.tune("kin_sig", 1)
-
-
-class Guarded:
-    """N rows of `width` values of `dtype` with GUARD rows of the NaN pattern either side, as one device allocation"""
-
-    def __init__(self, torch, N, width, dtype):
-        self.N, self.w = N, width
-        self.itype, self.pattern = (torch.int64, NAN64) if dtype == "float64" else (torch.int32, NAN32)
-        self.bits = torch.full(((N + 2 * GUARD) * width,), self.pattern, dtype=self.itype, device="cuda")
-        self.ptr = C.c_void_p(self.bits.data_ptr() + GUARD * width * self.bits.element_size())
-        self.ftype = torch.float64 if dtype == "float64" else torch.float32
-
-    def guards_intact(self):
-        g = GUARD * self.w
-        return bool((self.bits[:g] == self.pattern).all()) and bool((self.bits[g + self.N * self.w:] == self.pattern).all())
-
-    def live_bits(self):
-        g = GUARD * self.w
-        return self.bits[g:g + self.N * self.w]
-
-    def live(self):
-        return self.live_bits().view(self.ftype).reshape(self.N, self.w)
 
 
 def _launch(torch, ets, q, form, dtype):

@@ -9,59 +9,11 @@ import numpy.testing as nt
 import pytest
 
 import rtbhip
-from rtbhip import _lib
-from rtbhip._lib import lib, check, MEM_HOST, MEM_DEVICE
+from flush_guard import Out, both_ways
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 65]
-
-
-class Out:
-    """An output array of the call: shape and dtype."""
-
-    def __init__(self, *shape, dtype=np.float64):
-        self.shape, self.dtype = shape, dtype
-
-
-def both_ways(fn, make_args):
-    """Call `fn` twice -- make_args(ptr, mem, stream) builds the argument tuple, ptr(x) giving the address of input array / Out x in the
-    memory kind of that call -- and compare every Out of the host call with the device call's, bit for bit.  -> the host results."""
-    import torch
-    results = []
-    for mem in (MEM_HOST, MEM_DEVICE):
-        keep, outs = [], []
-
-        def ptr(x):
-            if x is None:
-                return None
-            if isinstance(x, Out):
-                a = np.full(x.shape, 123, dtype=x.dtype)          # never left as allocated: an output the call skips shows
-                outs.append(None)
-                slot = len(outs) - 1
-            else:
-                a, slot = np.ascontiguousarray(x), None
-            if mem == MEM_HOST:
-                keep.append(a)
-                if slot is not None:
-                    outs[slot] = a
-                return a.ctypes.data
-            t = torch.from_numpy(a).cuda()
-            keep.append(t)
-            if slot is not None:
-                outs[slot] = t
-            return t.data_ptr()
-        stream = None if mem == MEM_HOST else _lib.current_stream_ptr()
-        check(getattr(lib(), fn)(*make_args(ptr, mem, stream)))
-        if mem == MEM_DEVICE:
-            torch.cuda.synchronize()
-            outs = [t.cpu().numpy() for t in outs]
-        results.append(outs)
-    assert len(results[0]) == len(results[1]) > 0
-    for h, d in zip(*results):
-        nt.assert_array_equal(h, d)
-        assert not np.all(h == 123)
-    return results[0]
 
 
 @pytest.fixture(scope="module")
