@@ -353,6 +353,15 @@ int rtbhip_coriolis(rtbhip_dyn_t dyn, const double *q, const double *qd, int64_t
 int rtbhip_accel(rtbhip_dyn_t dyn, const double *q, const double *qd, const double *torque, int64_t N,
                  const double *grav3, double *qdd, int32_t mem, void *stream);
 
+/* VECTOR-JACOBIAN PRODUCT of rtbhip_inertia -- the backward pass of a loss on the inertia matrices; no reference counterpart.  gM (N,n,n),
+ * row-major, is the loss's gradient with respect to what rtbhip_inertia returns;
+ *   gq[r,k] = sum_ij gM[r,i,j] d M[r,i,j] / d q[r,k]      (N,n).
+ * gM need not be symmetric: every entry of M is an output in its own right, and where the forward kernel mirrors a computed entry both
+ * mirrored entries feed it.  The motor inertia G^2 Jm on the diagonal is a constant of q.  One fused kernel, one launch that reads q and gM once
+ * and writes gq once: chains of 1..8 joints in registers, 9..16 through a run-time-n kernel; RTBHIP_ELIMIT beyond 16 joints.  fp64.
+ * Chains whose links are all revolute; RTBHIP_EINVAL for a chain with a prismatic joint. */
+int rtbhip_inertia_vjp(rtbhip_dyn_t dyn, const double *q, int64_t N, const double *gM, double *gq, int32_t mem, void *stream);
+
 /* Robot.rne for ETS robots (robot/Robot.py:1704-1903): inverse dynamics over a tree of LINK
  * GROUPS -- every joint link together with the static links that precede it in link order (:1777-1789).
  * One rtbhip_tree_group per group, in the reference's order (parents before children):
@@ -394,6 +403,13 @@ int rtbhip_tree_inertia(rtbhip_tree_t tree, const double *q, int64_t N, double *
 int rtbhip_tree_coriolis(rtbhip_tree_t tree, const double *q, const double *qd, int64_t N, double *C, int32_t mem, void *stream);
 int rtbhip_tree_accel(rtbhip_tree_t tree, const double *q, const double *qd, const double *torque, int64_t N,
                       const double *gravity3, double *qdd, int32_t mem, void *stream);
+
+/* The vector-Jacobian product of rtbhip_tree_inertia: for the gradient gM (N,n,n) of a scalar loss with respect to the inertia matrices (not
+ * necessarily symmetric: both mirrored entries count), gq (N,n) = sum_ij gM[.,i,j] d M[.,i,j] / d q.  Every joint kind the forward call serves,
+ * for robots numbered in group order (link group j moves column j of q: every URDF robot, every robot whose joints were numbered automatically);
+ * RTBHIP_EINVAL for a hand-numbered robot.  One fused kernel, one launch: robots of 1..8 joints in registers, 9..20 through a run-time-n
+ * kernel; RTBHIP_ELIMIT beyond 20 joints.  fp64. */
+int rtbhip_tree_inertia_vjp(rtbhip_tree_t tree, const double *q, int64_t N, const double *gM, double *gq, int32_t mem, void *stream);
 
 /* Mixed fleet (BASELINE config 5): n_chains independent chains, each with its own batch; one
  * launch walks all of them (block -> chain map).  q[c] is (N[c], q_width_c), T[c] (N[c],4,4),

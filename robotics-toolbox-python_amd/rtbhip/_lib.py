@@ -68,6 +68,16 @@ class _sf(_st):
     """`void *stream` of rtbhip_link_frames_vjp: as _sp, a type of its own; its refusal rows and census are in tests/test_link_frames_vjp.py."""
 
 
+class _si(C.c_void_p):
+    """`void *stream` of rtbhip_inertia_vjp / rtbhip_tree_inertia_vjp: a void pointer for the call, a type of its own in this table and NOT a subclass
+    of _sp (the earlier censuses claim every row whose stream type is _sp or derives from it); their refusal rows and census are in
+    tests/test_inertia_vjp.py."""
+
+    @classmethod
+    def from_param(cls, value):
+        return C.c_void_p.from_param(value)
+
+
 # name -> (restype, argtypes); must list every symbol include/rtbhip.h declares
 SIGNATURES = {
     "rtbhip_last_error": (C.c_char_p, []),
@@ -128,9 +138,11 @@ SIGNATURES = {
     "rtbhip_tree_rne": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "rtbhip_tree_rne_vjp": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _st]),
     "rtbhip_tree_inertia": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp]),
+    "rtbhip_tree_inertia_vjp": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _si]),
     "rtbhip_tree_coriolis": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp]),
     "rtbhip_tree_accel": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "rtbhip_inertia": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp]),
+    "rtbhip_inertia_vjp": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _si]),
     "rtbhip_coriolis": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp]),
     "rtbhip_accel": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "rtbhip_fleet_fkine_jacob": (C.c_int, [C.POINTER(_u64), _i32, C.POINTER(_vp), C.POINTER(_i64), _i32,
@@ -261,6 +273,12 @@ def wants_grad(q):
         return False
     import torch
     return torch.is_grad_enabled()
+
+
+def is_f64(q):
+    """q is a float64 torch tensor (the element type of the entry points that have no float32 form)"""
+    import torch
+    return is_torch(q) and q.dtype == torch.float64
 
 
 def device_dtype(tensors, f32_ok=False, what="device inputs"):

@@ -18,7 +18,10 @@ function theorem on  rne(q, qd, qdd) = torque).
 
 The dynamics of ETS / URDF robots (rtbhip/erobot.py routes here): _TreeRneVJP's backward is one launch of rtbhip_tree_rne_vjp -- every joint kind
 the forward kernel serves, float64 -- and _TreeAccelVJP is _AccelVJP's construction on it, for robots numbered in group order (M symmetric).
-inertia, coriolis: not differentiable, unchanged."""
+
+The inertia matrix (rtbhip/dh.py and rtbhip/erobot.py route `inertia(q)` here: all-revolute DH chains, link trees numbered in group order; float64):
+_InertiaVJP / _TreeInertiaVJP's backward is one launch of rtbhip_inertia_vjp / rtbhip_tree_inertia_vjp, which reads q and the incoming (N, n, n)
+gradient once and writes gq once.  coriolis: not differentiable, unchanged."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -245,3 +248,58 @@ def differentiable_tree_rne(robot, q, qd, qdd, gravity):
 def differentiable_tree_accel(robot, q, qd, torque, gravity):
     """ERobot.accel(q, qd, torque, gravity=) attached to the autograd graph of its inputs (robots numbered in group order)"""
     return _TreeAccelVJP.apply(q, qd, torque, robot, gravity)
+
+
+# ---------------------------------------------------------------- the joint-space inertia matrix, DH robots and link trees
+def _inertia_vjp(fn, handle, n, q, gM):
+    """rtbhip_inertia_vjp / rtbhip_tree_inertia_vjp on the current stream: the gradient of q, shaped like q"""
+    q2 = q.detach().reshape(-1, n).contiguous()
+    N = q2.shape[0]
+    g2 = gM.detach().to(q2.dtype).reshape(N, n, n).contiguous()          # (a .sum() loss delivers a stride-0 expanded tensor)
+    gq = torch.empty_like(q2)
+    check(fn(handle, C.c_void_p(q2.data_ptr()), N, C.c_void_p(g2.data_ptr()), C.c_void_p(gq.data_ptr()), MEM_DEVICE, current_stream_ptr()))
+    return gq.reshape(q.shape)
+
+
+class _InertiaVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, robot):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q)
+        ctx.robot = robot
+        return robot.inertia(q)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gM):
+        (q,) = ctx.saved_tensors
+        if gM is None:
+            return None, None
+        return _inertia_vjp(lib().rtbhip_inertia_vjp, ctx.robot._dyn_handle(), ctx.robot.n, q, gM), None
+
+
+class _TreeInertiaVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, robot):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q)
+        ctx.robot = robot
+        return robot.inertia(q)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gM):
+        (q,) = ctx.saved_tensors
+        if gM is None:
+            return None, None
+        return _inertia_vjp(lib().rtbhip_tree_inertia_vjp, ctx.robot._handle(), ctx.robot.n, q, gM), None
+
+
+def differentiable_inertia(robot, q):
+    """DHRobot.inertia(q) attached to the autograd graph of q (all-revolute chains): the backward pass is one launch of rtbhip_inertia_vjp"""
+    return _InertiaVJP.apply(q, robot)
+
+
+def differentiable_tree_inertia(robot, q):
+    """ERobot.inertia(q) attached to the autograd graph of q (robots numbered in group order): the backward pass is one launch of rtbhip_tree_inertia_vjp"""
+    return _TreeInertiaVJP.apply(q, robot)

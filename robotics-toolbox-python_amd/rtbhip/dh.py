@@ -586,7 +586,12 @@ class DHRobot(RobotKinematics):
 
     def inertia(self, q):
         """Joint-space inertia matrix: (n,n) or (N,n,n) (reference Dynamics.inertia robot/Dynamics.py:704-763:
-        n rne calls per configuration; here one kernel pass per unit acceleration inside one lane)."""
+        n rne calls per configuration; here one kernel pass per unit acceleration inside one lane).
+        A float64 CUDA q that requires grad (gradients enabled) makes M differentiable with respect to q -- all-revolute chains: the same forward
+        call, one launch of rtbhip_inertia_vjp in the backward pass (rtbhip/autograd.py)."""
+        if self._wants_grad(q) and _lib.is_f64(q):
+            from . import autograd
+            return autograd.differentiable_inertia(self, q)
         arrs, N, single, tm, ptr, stream, mem, dev = self._dyn_args([q])
         M = self._empty((N, self.n, self.n), tm, dev)
         check(lib().rtbhip_inertia(self._dyn_handle(), ptr(arrs[0]), N, ptr(M), mem, stream))

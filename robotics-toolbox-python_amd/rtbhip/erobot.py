@@ -534,7 +534,13 @@ class ERobot(RobotKinematics):
 
     def inertia(self, q):
         """Joint-space inertia matrix: (n,n) or (N,n,n) (reference Dynamics.inertia robot/Dynamics.py:704-763: n Robot.rne calls per
-        configuration, row i = rne(q, 0, e_i) without gravity; here all passes of a configuration in one lane, csrc/tree_device.h)."""
+        configuration, row i = rne(q, 0, e_i) without gravity; here all passes of a configuration in one lane, csrc/tree_device.h).
+        A float64 CUDA q that requires grad (gradients enabled) makes M differentiable with respect to q when the joints are numbered in group
+        order (the default numbering), for every joint kind: the same forward call, one launch of rtbhip_tree_inertia_vjp in the backward pass;
+        a hand-numbered robot takes the ordinary path (rtbhip/autograd.py)."""
+        if self.n > 0 and _lib.wants_grad(q) and _lib.is_f64(q) and self._in_group_order():
+            from . import autograd
+            return autograd.differentiable_tree_inertia(self, q)
         arrs, N, single, ptr, stream, mem, empty = self._dyn_args([q])
         M = empty((N, self.n, self.n))
         check(lib().rtbhip_tree_inertia(self._handle(), ptr(arrs[0]), N, ptr(M), mem, stream))
