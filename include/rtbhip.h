@@ -362,6 +362,17 @@ int rtbhip_accel(rtbhip_dyn_t dyn, const double *q, const double *qd, const doub
  * Chains whose links are all revolute; RTBHIP_EINVAL for a chain with a prismatic joint. */
 int rtbhip_inertia_vjp(rtbhip_dyn_t dyn, const double *q, int64_t N, const double *gM, double *gq, int32_t mem, void *stream);
 
+/* The gradient of a loss on rtbhip_coriolis's matrices with respect to q and qd:
+ *     gq [r,m] = sum_jk gC[r,j,k] d C[r,j,k] / d q [r,m]        gqd[r,m] = sum_jk gC[r,j,k] d C[r,j,k] / d qd[r,m]
+ * gC (N, n, n) row-major, gq and gqd (N, n); either output may be NULL (not written), both NULL is refused.  What is differentiated is what
+ * rtbhip_coriolis returns (friction removed): C[j,k] = 1/2 B_j(qd, e_k) of the two-field Newton-Euler pass.  B_j is linear in its second field, so
+ * pass j of the adjoint carries the joint rates gC[j,:] in that field and is seeded with the single torque 1/2 on joint j; gqd is the adjoint of
+ * the first field's joint rates in the same sweeps.  Both results are linear in qd, exactly so under a power of two.  One fused kernel, one
+ * launch that reads q, qd and gC once and writes each gradient once: chains of 1..8 joints in registers, 9..16 through a run-time-n kernel;
+ * RTBHIP_ELIMIT beyond 16 joints.  fp64.  Chains whose links are all revolute; RTBHIP_EINVAL for a chain with a prismatic joint. */
+int rtbhip_coriolis_vjp(rtbhip_dyn_t dyn, const double *q, const double *qd, int64_t N, const double *gC, double *gq, double *gqd, int32_t mem,
+                        void *stream);
+
 /* Robot.rne for ETS robots (robot/Robot.py:1704-1903): inverse dynamics over a tree of LINK
  * GROUPS -- every joint link together with the static links that precede it in link order (:1777-1789).
  * One rtbhip_tree_group per group, in the reference's order (parents before children):
@@ -410,6 +421,13 @@ int rtbhip_tree_accel(rtbhip_tree_t tree, const double *q, const double *qd, con
  * RTBHIP_EINVAL for a hand-numbered robot.  One fused kernel, one launch: robots of 1..8 joints in registers, 9..20 through a run-time-n
  * kernel; RTBHIP_ELIMIT beyond 20 joints.  fp64. */
 int rtbhip_tree_inertia_vjp(rtbhip_tree_t tree, const double *q, int64_t N, const double *gM, double *gq, int32_t mem, void *stream);
+
+/* The gradient of a loss on rtbhip_tree_coriolis's matrices with respect to q and qd, as rtbhip_coriolis_vjp: gC (N, n, n), gq and gqd (N, n),
+ * either output may be NULL, both NULL is refused.  Every joint kind the forward call serves, for robots numbered in group order (link group j
+ * moves column j of q); RTBHIP_EINVAL for a hand-numbered robot.  One fused kernel, one launch: robots of 1..8 joints in registers, 9..20
+ * through a run-time-n kernel; RTBHIP_ELIMIT beyond 20 joints.  fp64. */
+int rtbhip_tree_coriolis_vjp(rtbhip_tree_t tree, const double *q, const double *qd, int64_t N, const double *gC, double *gq, double *gqd,
+                             int32_t mem, void *stream);
 
 /* Mixed fleet (BASELINE config 5): n_chains independent chains, each with its own batch; one
  * launch walks all of them (block -> chain map).  q[c] is (N[c], q_width_c), T[c] (N[c],4,4),

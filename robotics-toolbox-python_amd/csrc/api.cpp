@@ -658,6 +658,11 @@ __attribute__((weak)) int launch_frames_vjp(const Chain *c, const DevChain &dc, 
 __attribute__((weak)) int launch_inertia_vjp(const Dyn *d, const DevLink *links, const double *q, int64_t N, const double *gM, double *gq, hipStream_t s);
 __attribute__((weak)) int launch_tree_inertia_vjp(const Tree *t, const DevGroup *groups, const double *q, int64_t N, const double *gM, double *gq,
                                                   hipStream_t s);
+// ... and of the two Coriolis-matrix adjoints (coriolis_vjp_kernels.hip, tree_coriolis_vjp_kernels.hip), weak for the same reason
+__attribute__((weak)) int launch_coriolis_vjp(const Dyn *d, const DevLink *links, const double *q, const double *qd, int64_t N, const double *gC,
+                                              double *gq, double *gqd, hipStream_t s);
+__attribute__((weak)) int launch_tree_coriolis_vjp(const Tree *t, const DevGroup *groups, const double *q, const double *qd, int64_t N,
+                                                   const double *gC, double *gq, double *gqd, hipStream_t s);
 namespace {
 
 // rtbhip_rne_vjp / rtbhip_rne_vjp_f32: the gradient of a loss on rtbhip_rne's torques with respect to q, qd and qdd (k_rne_vjp)
@@ -1452,6 +1457,35 @@ int rtbhip_coriolis(rtbhip_dyn_t dyn, const double *q, const double *qd, int64_t
     return dyn_entry("coriolis", dyn, 1, q, qd, nullptr, N, nullptr, Cm, mem, stream);
 }
 
+// the gradient of a loss on rtbhip_coriolis's matrices with respect to q and qd (k_coriolis_vjp); gq or gqd NULL: not wanted
+int rtbhip_coriolis_vjp(rtbhip_dyn_t dyn, const double *q, const double *qd, int64_t N, const double *gC, double *gq, double *gqd, int32_t mem,
+                        void *stream)
+{
+    const char *fn = "coriolis_vjp";
+    RTB_TRACE(fn);
+    const std::shared_ptr<Dyn> d_owner = dyn_from_handle(dyn);
+    Dyn *d = d_owner.get();
+    if (!d) return refuse(fn, "unknown dyn handle");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    if (N == 0) return RTBHIP_OK;                            // an empty batch: no pointer is looked at
+    if (!qd) return refuse(fn, "NULL input with N > 0");
+    if (!gC) return refuse(fn, "NULL gC");
+    if (!gq && !gqd) return refuse(fn, "NULL gq and NULL gqd");
+    if (d->n < 1 || d->n > 16) return refuse(fn, "chains of 1..16 joints", RTBHIP_ELIMIT);          // rtbhip_coriolis's built-in sizes
+    for (const DevLink &l : d->links)
+        if (l.sigma != 0) return refuse(fn, "chain has a prismatic joint");
+    if (!launch_coriolis_vjp) return refuse(fn, "not built into this library");
+    const DevLink *links = nullptr;
+    RTB_TRY(dyn_device_links(d, &links));
+    const size_t bytes = (size_t)N * (size_t)d->n * 8;
+    Staged st(mem, stream);
+    const double *dq = st.in(q, bytes), *dqd = st.in(qd, bytes), *dg = st.in(gC, bytes * (size_t)d->n);
+    double *dgq = gq ? st.out(gq, bytes) : nullptr, *dgqd = gqd ? st.out(gqd, bytes) : nullptr;
+    RTB_TRY(st.status());
+    return st.finish(launch_coriolis_vjp(d, links, dq, dqd, N, dg, dgq, dgqd, st.stream()));
+}
+
 int rtbhip_accel(rtbhip_dyn_t dyn, const double *q, const double *qd, const double *torque, int64_t N,
                  const double *grav3, double *qdd, int32_t mem, void *stream)
 {
@@ -1494,6 +1528,36 @@ int rtbhip_tree_inertia_vjp(rtbhip_tree_t tree, const double *q, int64_t N, cons
 int rtbhip_tree_coriolis(rtbhip_tree_t tree, const double *q, const double *qd, int64_t N, double *Cm, int32_t mem, void *stream)
 {
     return tree_dyn_entry("tree_coriolis", tree, 1, q, qd, nullptr, N, nullptr, Cm, mem, stream);
+}
+
+// the gradient of a loss on rtbhip_tree_coriolis's matrices with respect to q and qd (k_tree_coriolis_vjp); gq or gqd NULL: not wanted
+int rtbhip_tree_coriolis_vjp(rtbhip_tree_t tree, const double *q, const double *qd, int64_t N, const double *gC, double *gq, double *gqd, int32_t mem,
+                             void *stream)
+{
+    const char *fn = "tree_coriolis_vjp";
+    const std::shared_ptr<Tree> t_owner = tree_from_handle(tree);
+    Tree *t = t_owner.get();
+    RTB_TRACE(fn);
+    if (!t) return refuse(fn, "unknown tree handle");
+    DeviceScope dscope;
+    RTB_TRY(check_batch(fn, q, N, mem, &dscope));
+    if (N == 0) return RTBHIP_OK;                            // an empty batch: no pointer is looked at
+    if (!qd) return refuse(fn, "NULL input with N > 0");
+    if (!gC) return refuse(fn, "NULL gC");
+    if (!gq && !gqd) return refuse(fn, "NULL gq and NULL gqd");
+    if (t->n < 1 || t->n > 20) return refuse(fn, "robots of 1..20 joints", RTBHIP_ELIMIT);          // rtbhip_tree_coriolis's built-in sizes
+    for (int j = 0; j < t->n; ++j)
+        if (jm_jq(t->groups[j].jmeta) != j)
+            return refuse(fn, "the robot is not numbered in group order (joint j of the q row must be moved by link group j)");
+    if (!launch_tree_coriolis_vjp) return refuse(fn, "not built into this library");
+    const DevGroup *groups = nullptr;
+    RTB_TRY(tree_device_groups(t, &groups));
+    const size_t bytes = (size_t)N * (size_t)t->n * 8;
+    Staged st(mem, stream);
+    const double *dq = st.in(q, bytes), *dqd = st.in(qd, bytes), *dg = st.in(gC, bytes * (size_t)t->n);
+    double *dgq = gq ? st.out(gq, bytes) : nullptr, *dgqd = gqd ? st.out(gqd, bytes) : nullptr;
+    RTB_TRY(st.status());
+    return st.finish(launch_tree_coriolis_vjp(t, groups, dq, dqd, N, dg, dgq, dgqd, st.stream()));
 }
 
 int rtbhip_tree_accel(rtbhip_tree_t tree, const double *q, const double *qd, const double *torque, int64_t N,

@@ -78,6 +78,16 @@ class _si(C.c_void_p):
         return C.c_void_p.from_param(value)
 
 
+class _sc(C.c_void_p):
+    """`void *stream` of rtbhip_coriolis_vjp / rtbhip_tree_coriolis_vjp: as _si, a void pointer for the call and a type of its own in this table --
+    neither _vp, nor _si, nor a subclass of _sp, whose censuses claim rows by exactly those types; their refusal rows and census are in
+    tests/test_coriolis_vjp.py."""
+
+    @classmethod
+    def from_param(cls, value):
+        return C.c_void_p.from_param(value)
+
+
 # name -> (restype, argtypes); must list every symbol include/rtbhip.h declares
 SIGNATURES = {
     "rtbhip_last_error": (C.c_char_p, []),
@@ -140,10 +150,12 @@ SIGNATURES = {
     "rtbhip_tree_inertia": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp]),
     "rtbhip_tree_inertia_vjp": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _si]),
     "rtbhip_tree_coriolis": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp]),
+    "rtbhip_tree_coriolis_vjp": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _sc]),
     "rtbhip_tree_accel": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "rtbhip_inertia": (C.c_int, [_u64, _vp, _i64, _vp, _i32, _vp]),
     "rtbhip_inertia_vjp": (C.c_int, [_u64, _vp, _i64, _vp, _vp, _i32, _si]),
     "rtbhip_coriolis": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp]),
+    "rtbhip_coriolis_vjp": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _sc]),
     "rtbhip_accel": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
     "rtbhip_fleet_fkine_jacob": (C.c_int, [C.POINTER(_u64), _i32, C.POINTER(_vp), C.POINTER(_i64), _i32,
                                            C.POINTER(_vp), C.POINTER(_vp), _i32, _vp]),

@@ -21,7 +21,10 @@ the forward kernel serves, float64 -- and _TreeAccelVJP is _AccelVJP's construct
 
 The inertia matrix (rtbhip/dh.py and rtbhip/erobot.py route `inertia(q)` here: all-revolute DH chains, link trees numbered in group order; float64):
 _InertiaVJP / _TreeInertiaVJP's backward is one launch of rtbhip_inertia_vjp / rtbhip_tree_inertia_vjp, which reads q and the incoming (N, n, n)
-gradient once and writes gq once.  coriolis: not differentiable, unchanged."""
+gradient once and writes gq once.
+
+The Coriolis matrix (`coriolis(q, qd)`, the same robots, float64): _CoriolisVJP / _TreeCoriolisVJP's backward is one launch of rtbhip_coriolis_vjp /
+rtbhip_tree_coriolis_vjp, which returns the gradients of q and qd that autograd asks for (ctx.needs_input_grad) and no others."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -303,3 +306,65 @@ def differentiable_inertia(robot, q):
 def differentiable_tree_inertia(robot, q):
     """ERobot.inertia(q) attached to the autograd graph of q (robots numbered in group order): the backward pass is one launch of rtbhip_tree_inertia_vjp"""
     return _TreeInertiaVJP.apply(q, robot)
+
+
+# ---------------------------------------------------------------- the Coriolis / centripetal matrix, DH robots and link trees
+def _coriolis_vjp(fn, handle, n, q, qd, gC, want):
+    """rtbhip_coriolis_vjp / rtbhip_tree_coriolis_vjp on the current stream: the gradients of q and qd named by `want`, each shaped like its input"""
+    q2 = q.detach().reshape(-1, n).contiguous()
+    qd2 = qd.detach().to(q2.dtype).reshape(-1, n).contiguous()
+    N = q2.shape[0]
+    g2 = gC.detach().to(q2.dtype).reshape(N, n, n).contiguous()          # (a .sum() loss delivers a stride-0 expanded tensor)
+    outs = [torch.empty_like(q2) if w else None for w in want]
+    ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+    check(fn(handle, ptr(q2), ptr(qd2), N, ptr(g2), ptr(outs[0]), ptr(outs[1]), MEM_DEVICE, current_stream_ptr()))
+    return [None if o is None else o.reshape(x.shape) for o, x in zip(outs, (q, qd))]
+
+
+class _CoriolisVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, qd, robot):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, qd)
+        ctx.robot = robot
+        return robot.coriolis(q, qd)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gC):
+        q, qd = ctx.saved_tensors
+        want = [bool(w) for w in ctx.needs_input_grad[:2]]
+        if gC is None or not any(want):
+            return None, None, None
+        gq, gqd = _coriolis_vjp(lib().rtbhip_coriolis_vjp, ctx.robot._dyn_handle(), ctx.robot.n, q, qd, gC, want)
+        return gq, gqd, None
+
+
+class _TreeCoriolisVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, qd, robot):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, qd)
+        ctx.robot = robot
+        return robot.coriolis(q, qd)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gC):
+        q, qd = ctx.saved_tensors
+        want = [bool(w) for w in ctx.needs_input_grad[:2]]
+        if gC is None or not any(want):
+            return None, None, None
+        gq, gqd = _coriolis_vjp(lib().rtbhip_tree_coriolis_vjp, ctx.robot._handle(), ctx.robot.n, q, qd, gC, want)
+        return gq, gqd, None
+
+
+def differentiable_coriolis(robot, q, qd):
+    """DHRobot.coriolis(q, qd) attached to the autograd graph of q and qd (all-revolute chains): the backward pass is one launch of rtbhip_coriolis_vjp"""
+    return _CoriolisVJP.apply(q, qd, robot)
+
+
+def differentiable_tree_coriolis(robot, q, qd):
+    """ERobot.coriolis(q, qd) attached to the autograd graph of q and qd (robots numbered in group order): the backward pass is one launch of
+    rtbhip_tree_coriolis_vjp"""
+    return _TreeCoriolisVJP.apply(q, qd, robot)

@@ -600,7 +600,12 @@ class DHRobot(RobotKinematics):
     def coriolis(self, q, qd):
         """Coriolis/centripetal matrix C(q, qd): (n,n) or (N,n,n)
         (reference Dynamics.coriolis robot/Dynamics.py:765-861: n + n(n-1)/2 frictionless rne calls; here the same matrix from
-        n two-field passes -- column k is the bilinear form B(qd, e_k) of the velocity torque, csrc/dyn_device.h)."""
+        n two-field passes -- column k is the bilinear form B(qd, e_k) of the velocity torque, csrc/dyn_device.h).
+        Float64 CUDA q and qd of which one requires grad (gradients enabled) make C differentiable with respect to both -- all-revolute chains:
+        the same forward call, one launch of rtbhip_coriolis_vjp in the backward pass (rtbhip/autograd.py)."""
+        if self._wants_grad(q, qd) and _lib.is_f64(q) and _lib.is_f64(qd) and q.is_cuda and qd.is_cuda:
+            from . import autograd
+            return autograd.differentiable_coriolis(self, q, qd)
         arrs, N, single, tm, ptr, stream, mem, dev = self._dyn_args([q, qd])
         Cm = self._empty((N, self.n, self.n), tm, dev)
         check(lib().rtbhip_coriolis(self._dyn_handle(), ptr(arrs[0]), ptr(arrs[1]), N, ptr(Cm), mem, stream))

@@ -548,7 +548,14 @@ class ERobot(RobotKinematics):
 
     def coriolis(self, q, qd):
         """Coriolis / centripetal matrix C(q, qd): (n,n) or (N,n,n) (reference Dynamics.coriolis robot/Dynamics.py:765-861:
-        n + n(n-1)/2 Robot.rne calls per configuration; here n two-field passes, column k = B(qd, e_k): csrc/tree_device.h tree_bilinear_core)."""
+        n + n(n-1)/2 Robot.rne calls per configuration; here n two-field passes, column k = B(qd, e_k): csrc/tree_device.h tree_bilinear_core).
+        Float64 CUDA q and qd of which one requires grad (gradients enabled) make C differentiable with respect to both when the joints are
+        numbered in group order (the default numbering), for every joint kind: the same forward call, one launch of rtbhip_tree_coriolis_vjp in
+        the backward pass; a hand-numbered robot takes the ordinary path (rtbhip/autograd.py)."""
+        if (self.n > 0 and (_lib.wants_grad(q) or _lib.wants_grad(qd)) and _lib.is_f64(q) and _lib.is_f64(qd) and q.is_cuda and qd.is_cuda
+                and self._in_group_order()):
+            from . import autograd
+            return autograd.differentiable_tree_coriolis(self, q, qd)
         arrs, N, single, ptr, stream, mem, empty = self._dyn_args([q, qd])
         Cm = empty((N, self.n, self.n))
         check(lib().rtbhip_tree_coriolis(self._handle(), ptr(arrs[0]), ptr(arrs[1]), N, ptr(Cm), mem, stream))

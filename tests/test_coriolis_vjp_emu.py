@@ -1,0 +1,147 @@
+"""The adjoint of the Coriolis / centripetal matrix on the CPU (no GPU needed): the per-lane bodies of k_coriolis_vjp (csrc/coriolis_vjp_kernels.hip:
+coriolis_vjp_lane) and k_tree_coriolis_vjp (csrc/tree_coriolis_vjp_kernels.hip: tree_coriolis_vjp_lane) compiled host-side by this test
+(tests/emu_coriolis_vjp/emu_coriolis_vjp.cpp, linked against tests/emu/libemu.so for the table compilers) and held against the oracle of
+tests/coriolis_vjp_cases.py -- Richardson differences of the reference's Coriolis matrix for gq, its exact linearity in qd for gqd, contracted with
+gC -- at 1e-9 max(1, |ref|max).  The device runs the same source through another compiler: tests/test_coriolis_vjp.py."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import emu_harness
+import coriolis_vjp_cases as cases
+from test_inertia_vjp_emu import dyn_handle, tree_handle
+
+ROOT = emu_harness.ROOT
+SRC = os.path.join(ROOT, "tests", "emu_coriolis_vjp", "emu_coriolis_vjp.cpp")
+SO = os.path.join(ROOT, "tests", "emu_coriolis_vjp", "libemu_coriolis_vjp.so")
+UNITS = [os.path.join(ROOT, "robotics-toolbox-python_amd", "csrc", f) for f in ("coriolis_vjp_kernels.hip", "tree_coriolis_vjp_kernels.hip")]
+_vp, _u64, _i64, _i32 = C.c_void_p, C.c_uint64, C.c_int64, C.c_int32
+SIZES = (1, 63, 64, 65, 130)          # the tile edge
+
+
+@pytest.fixture(scope="module")
+def lib():
+    base = emu_harness.lib()                     # libemu.so: the table compilers and registries (built if stale)
+    import __graft_entry__ as g
+    digest = g.source_digest(emu_harness._deps() + [SRC] + UNITS)
+    stamp = SO + ".stamp"
+    if not (os.path.exists(SO) and os.path.exists(stamp) and open(stamp).read().strip() == digest):
+        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+        emu_dir = os.path.dirname(emu_harness.EMU_SO)
+        subprocess.check_call([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-x", "hip", "-w", "-I" + os.path.join(ROOT, "include"),
+                               "-shared", SRC, "-o", SO, "-L" + emu_dir, "-l:libemu.so", "-Wl,-rpath," + emu_dir])
+        open(stamp, "w").write(digest)
+    so = C.CDLL(SO)
+    so.emu_coriolis_vjp.argtypes = [_u64, _vp, _vp, _i64, _vp, _vp, _vp, _i32]
+    so.emu_tree_coriolis_vjp.argtypes = [_u64, _vp, _vp, _i64, _vp, _vp, _vp, _i32]
+    assert base is not None
+    return so
+
+
+def _run(fn, handle, q, qd, g, force_rt=False, want=0, which=(True, True)):
+    """(gq, gqd); an output not asked for is handed over as NULL and comes back as None"""
+    p = emu_harness._p
+    q, qd, g = (np.ascontiguousarray(x, dtype=np.float64) for x in (q, qd, g))
+    outs = [np.full(q.shape, np.nan) if w else None for w in which]
+    assert fn(handle, p(q), p(qd), q.shape[0], p(g), *(None if o is None else p(o) for o in outs), int(force_rt)) == want
+    return outs
+
+
+def _check(tag, name, got, ref):
+    for what, a, b in zip(("gq", "gqd"), got, ref):
+        err = cases.rel_err(a, b)
+        print("coriolis_vjp lane %s %s %s: rel err %.3e (|ref|max %.3g)" % (tag, name, what, err, np.abs(b).max()))
+        assert err <= cases.BOUND, (name, what, err)
+
+
+@pytest.mark.parametrize("name", sorted(cases.DH_ROBOTS))
+def test_dh_lane_body_equals_the_oracle(lib, name):
+    rb, q, qd, g, rq, rd = cases.dh_case(name)
+    both = _run(lib.emu_coriolis_vjp, dyn_handle(rb), q, qd, g)
+    _check("dh", name, both, (rq, rd))
+    # each gradient alone: the same bits
+    assert np.array_equal(_run(lib.emu_coriolis_vjp, dyn_handle(rb), q, qd, g, which=(True, False))[0], both[0])
+    assert np.array_equal(_run(lib.emu_coriolis_vjp, dyn_handle(rb), q, qd, g, which=(False, True))[1], both[1])
+
+
+@pytest.mark.parametrize("name", cases.TREES)
+def test_tree_lane_body_equals_the_oracle(lib, name):
+    rob, orc, q, qd, g, rq, rd = cases.tree_case(name)
+    both = _run(lib.emu_tree_coriolis_vjp, tree_handle(rob), q, qd, g)
+    _check("tree", name, both, (rq, rd))
+    assert np.array_equal(_run(lib.emu_tree_coriolis_vjp, tree_handle(rob), q, qd, g, which=(True, False))[0], both[0])
+    assert np.array_equal(_run(lib.emu_tree_coriolis_vjp, tree_handle(rob), q, qd, g, which=(False, True))[1], both[1])
+
+
+@pytest.mark.parametrize("N", SIZES)
+@pytest.mark.parametrize("name", ["puma560", "n9s", "UR5", "tree9"])
+def test_batch_sizes_at_the_tile_edge(lib, name, N):
+    rb, q, qd, g, rq, rd = cases.case(name, N)
+    tree = name in cases.TREES
+    got = _run(lib.emu_tree_coriolis_vjp if tree else lib.emu_coriolis_vjp, (tree_handle if tree else dyn_handle)(rb), q, qd, g)
+    assert got[0].shape == (N, rb.n) and cases.rel_err(got[0], rq) <= cases.BOUND and cases.rel_err(got[1], rd) <= cases.BOUND
+
+
+@pytest.mark.parametrize("name", ["puma560", "panda", "n1s", "n3s", "n8m"])
+def test_dh_run_time_n_form_agrees(lib, name):
+    """the NJ = 0 body (private-memory tape, one row of gC staged per pass) on chains the compile-time body also serves"""
+    rb, q, qd, g, rq, rd = cases.dh_case(name)
+    _check("dh-rt", name, _run(lib.emu_coriolis_vjp, dyn_handle(rb), q, qd, g, force_rt=True), (rq, rd))
+
+
+@pytest.mark.parametrize("name", ["one_p", "chain8", "tree5", "tree8", "UR5"])
+def test_tree_run_time_n_form_agrees(lib, name):
+    """the NG = 0 body (private-memory tape, one row of gC staged per pass) on robots the compile-time body also serves"""
+    rob, orc, q, qd, g, rq, rd = cases.tree_case(name)
+    _check("tree-rt", name, _run(lib.emu_tree_coriolis_vjp, tree_handle(rob), q, qd, g, force_rt=True), (rq, rd))
+
+
+@pytest.mark.parametrize("name", ["panda", "UR5"])
+def test_homogeneity_in_qd(lib, name):
+    """gq(q, 2^40 qd) = 2^40 gq(q, qd) and gqd(q, 2^40 qd) = gqd(q, qd), per row at 1e-13 of the row's largest magnitude: a two-field adjoint scales
+    exactly under a power of two, an evaluation of the polar identity at qd +- e_k loses about twelve digits there; qd = 0 gives gq = 0"""
+    rb, q, qd, g, rq, rd = cases.case(name, 8)
+    tree = name in cases.TREES
+    fn, h = (lib.emu_tree_coriolis_vjp if tree else lib.emu_coriolis_vjp), (tree_handle if tree else dyn_handle)(rb)
+    s = 2.0 ** 40
+    a, b = _run(fn, h, q, qd, g), _run(fn, h, q, s * qd, g)
+    for x, y in ((s * a[0], b[0]), (a[1], b[1])):
+        assert (np.abs(x - y).max(axis=1) <= 1e-13 * np.abs(x).max(axis=1)).all()
+    z = _run(fn, h, q, np.zeros_like(qd), g)
+    assert not z[0].any() and cases.rel_err(z[1], rd) <= cases.BOUND
+
+
+def test_one_joint_has_no_coriolis_matrix(lib):
+    """C of a chain of one joint is zero for every q and qd: no pass runs, both gradients are exact zeros"""
+    for name in ("n1s", "n1m"):
+        rb, q, qd, g, rq, rd = cases.dh_case(name)
+        got = _run(lib.emu_coriolis_vjp, dyn_handle(rb), q, qd, g)
+        assert not got[0].any() and not got[1].any() and np.abs(rq).max() <= 1e-9 and np.abs(rd).max() <= 1e-9
+
+
+def test_prismatic_chain_and_hand_numbered_tree_are_not_served(lib):
+    from rtbhip.dh import DHRobot, RevoluteDH, PrismaticDH
+    rb = DHRobot([RevoluteDH(a=0.3, m=1.0), PrismaticDH(alpha=0.5, m=1.0)])
+    _run(lib.emu_coriolis_vjp, dyn_handle(rb), np.zeros((1, 2)), np.zeros((1, 2)), np.zeros((1, 2, 2)), want=-2)
+    rob, _ = cases.tree_robot(cases.HAND)
+    _run(lib.emu_tree_coriolis_vjp, tree_handle(rob), np.zeros((1, rob.n)), np.zeros((1, rob.n)), np.zeros((1, rob.n, rob.n)), want=-3)
+
+
+def test_a_library_linked_without_the_kernel_units_loads_and_refuses(lib):
+    """tests/emu/libemu.so links the product's api.cpp.o with a fixed list of units that includes neither coriolis_vjp_kernels.hip nor
+    tree_coriolis_vjp_kernels.hip: the launchers are weak references there, the library loads, and the entry points say what is missing"""
+    emu = emu_harness.lib()
+    p = emu_harness._p
+    proto = C.CFUNCTYPE(C.c_int, _u64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp)       # a prototype of this test's own: the shared CDLL object is left as it is
+    rb = cases.dh_robot("puma560")
+    x, m = np.zeros((2, rb.n)), np.zeros((2, rb.n, rb.n))
+    assert proto(("rtbhip_coriolis_vjp", emu))(dyn_handle(rb), p(x), p(x), 2, p(m), p(x.copy()), p(x.copy()), 0, None) == -1
+    assert emu.rtbhip_last_error().decode() == "coriolis_vjp: not built into this library"
+    rob, _ = cases.tree_robot("chain3")
+    x, m = np.zeros((2, rob.n)), np.zeros((2, rob.n, rob.n))
+    assert proto(("rtbhip_tree_coriolis_vjp", emu))(tree_handle(rob), p(x), p(x), 2, p(m), p(x.copy()), p(x.copy()), 0, None) == -1
+    assert emu.rtbhip_last_error().decode() == "tree_coriolis_vjp: not built into this library"
