@@ -15,7 +15,14 @@ against its own stencil <= 2.0e-13 (test_coriolis_vjp.py::test_the_oracle_is_a_h
 Bound: the project's contract, 1e-9 max(1, |ref|max) over the compared array.
 Inputs: q ~ U(-3, 3), qd ~ U(-2, 2), gC ~ U(-1, 1).  The reference's Coriolis matrix costs n + n (n - 1) / 2 inverse-dynamics calls per row and the
 stencil 4 n of those, and the tree oracle is a Python loop (one erobot_coriolis row of YuMi: 0.12 s): a case draws a few distinct rows -- 8, or 2
-for the big trees -- and repeats them cyclically to N (tree_rne_vjp_cases.tiled); the oracle runs once on the distinct rows."""
+for the big trees -- and repeats them cyclically to N (tree_rne_vjp_cases.tiled); the oracle runs once on the distinct rows.
+
+What period-8 / period-2 inputs CANNOT see: row r and row r + 8 (r + 2) carry the same inputs and the same expected outputs, so a staging or flush
+error that moves a row by a multiple of the period (the tile's f / n, f % n index arithmetic, the per-pass restaging of the run-time-n forms)
+returns exactly the expected bits.  The cyclic cases serve test_gradients_equal_the_oracle and the guard-row test, where the oracle is needed on
+every row; rows that are all distinct are covered by tests/test_flush_guard_all_gpu.py (129 distinct rows per robot at every size of its table)
+and, in tests/test_coriolis_vjp.py, by test_rows_are_independent, test_fused_call_equals_the_composition and
+test_nonfinite_and_huge_joint_values_stay_in_their_row (draw() with no oracle: bit comparisons and the composition)."""
 import functools
 
 import numpy as np

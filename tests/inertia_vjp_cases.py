@@ -12,7 +12,14 @@ max(1, |ref|max): Puma560 7.1e-13, Panda 8.1e-13, UR5 6.2e-13 at h = 1e-3 -- ins
 stays (test_inertia_vjp.py::test_the_oracle_is_a_hundred_times_finer_than_the_bound holds it there).
 Bound: the project's contract, 1e-9 max(1, |ref|max) over the compared array.
 Inputs: q ~ U(-3, 3), gM ~ U(-1, 1), NOT symmetric: every entry of M is an output in its own right.  The tree oracle is a per-sample Python loop,
-so a tree case draws ROWS distinct rows and repeats them cyclically to N (tree_rne_vjp_cases.tiled); the oracle runs once on the ROWS rows."""
+so a tree case draws ROWS distinct rows and repeats them cyclically to N (tree_rne_vjp_cases.tiled); the oracle runs once on the ROWS rows.
+
+What period-8 inputs CANNOT see: row r and row r + 8 carry the same inputs and the same expected outputs, so a staging or flush error that moves a
+row by a multiple of 8 (the tile's f / n, f % n index arithmetic, the per-pass restaging of the run-time-n forms) returns exactly the expected
+bits.  The cyclic tree cases serve test_gradient_equals_the_oracle and the guard-row test, where the oracle is needed on every row; rows that are
+all distinct are covered by tests/test_flush_guard_all_gpu.py (129 distinct rows per robot at every size of its table) and, in
+tests/test_inertia_vjp.py, by test_rows_are_independent, test_fused_call_equals_the_composition and
+test_nonfinite_and_huge_joint_values_stay_in_their_row (draw() with no oracle: bit comparisons and the composition)."""
 import functools
 
 import numpy as np

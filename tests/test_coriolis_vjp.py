@@ -117,7 +117,8 @@ def test_the_rows_name_both_entry_points():
 # ------------------------------------------------------------------------------------------------ the oracle's own error (no GPU)
 @pytest.mark.parametrize("name", ["puma560", "panda", "UR5"])
 def test_the_oracle_is_a_hundred_times_finer_than_the_bound(name):
-    """the stencil at h against h / 2, and the exact gqd against its own stencil: <= 1e-11 max(1, |ref|max), a hundredth of the bound"""
+    """the stencil at h against h / 2, and the exact gqd against its own stencil: <= 1e-11 max(1, |ref|max), a hundredth of the bound; panda and
+    UR5 also with one joint at 2^21 + 0.25 rad, h = 2^-10 against h / 2"""
     if name == "UR5":
         rob, orc, q, qd, g, a, d = cases.tree_case(name)
         Cf = cases.tree_coriolis(orc)
@@ -130,6 +131,25 @@ def test_the_oracle_is_a_hundred_times_finer_than_the_bound(name):
     errd = float(np.abs(d - cases.gqd_stencil(Cf, q, qd, g)).max()) / max(1.0, float(np.abs(d).max()))
     print("coriolis oracle %s: gq h against h/2 %.3e (|ref|max %.3g); exact gqd against its stencil %.3e" % (name, err, np.abs(a).max(), errd))
     assert err <= 1e-11 and errd <= 1e-11
+    if name in ("panda", "UR5"):
+        # one joint at 2^21 + 0.25 rad, the stencil at h = 2^-10 against h / 2: the reference can supply the number that
+        # test_nonfinite_and_huge_joint_values_stay_in_their_row compares that row with
+        q, qd, g = (np.array(x) for x in cases.draw(q.shape[1], 2, 5))
+        q[:, 2] = BIG_ANGLE
+        a, b = _oracle(name, q, qd, g, BIG_H)[0], _oracle(name, q, qd, g, BIG_H / 2)[0]
+        err = float(np.abs(a - b).max()) / max(1.0, float(np.abs(a).max()))
+        print("coriolis oracle %s at a huge angle: gq h = 2^-10 against h/2 %.3e (|ref|max %.3g)" % (name, err, np.abs(a).max()))
+        assert err <= 1e-11
+
+
+BIG_ANGLE = 2.0 ** 21 + 0.25          # beyond 2^20: the wave of such a lane takes the library's sine and cosine (csrc/coriolis_vjp_kernels.hip:71, tree_trig)
+BIG_H = 2.0 ** -10                    # q +- h and q +- 2 h are exact doubles at that magnitude (one ulp is 2^-31); at h = 1e-3 they are not, six digits lost
+
+
+def _oracle(name, q, qd, g, h):
+    if name in cases.DH_ROBOTS:
+        return cases.dh_oracle(cases.dh_robot(name), q, qd, g, h=h)
+    return cases.tree_oracle(cases.tree_robot(name)[1], q, qd, g, h=h)
 
 
 # ------------------------------------------------------------------------------------------------ front-end routing (no GPU)
@@ -275,6 +295,23 @@ def _dev(torch, *arrays):
     return [None if a is None else torch.from_numpy(np.array(a)).cuda() for a in arrays]          # (a copy: the cases are read-only)
 
 
+def _distinct(name, N):
+    """(robot, q, qd, gC) of N DISTINCT rows from the cases' input distribution, no oracle: for comparisons of bits and of one device result with
+    another.  (cases.case repeats 8 or 2 rows, and there a row that lands a multiple of the period away still meets its expected bits.)"""
+    rb = cases.dh_robot(name) if name in cases.DH_ROBOTS else cases.tree_robot(name)[0]
+    return (rb,) + tuple(np.array(x) for x in cases.draw(rb.n, N, cases._seed(name) + 1))
+
+
+def _scales(name):
+    """max(1, |ref|max) of gq and gqd from the cached oracle rows of the same robot and the same input distribution"""
+    ref = cases.dh_case(name)[4:] if name in cases.DH_ROBOTS else cases.tree_case(name)[5:]
+    return [max(1.0, float(np.abs(r).max())) for r in ref]
+
+
+def _bits(a, b):
+    return a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
 SIZES = (1, 63, 64, 65, 130)
 ALL = sorted(cases.DH_ROBOTS) + cases.TREES
 BIG = set(cases.DH_BIG) | set(cases.TREE_BIG)              # 9 joints and more: the run-time-n kernels
@@ -306,13 +343,13 @@ def test_fused_call_equals_the_composition(name):
     """2 n launches of the existing adjoint at qd +- e_k, summed, against the one fused launch: within 2e-9 max(1, |ref|max) -- each is held to 1e-9 of
     the oracle"""
     torch = _torch()
-    rb, q, qd, g, rq, rd = cases.case(name, 65)
+    rb, q, qd, g = _distinct(name, 65)          # 65 distinct rows; the scale is the cached oracle rows'
     dq, dqd, dg = _dev(torch, q, qd, g)
     fused, comp = _vjp(rb, dq, dqd, dg), _composition(rb, dq, dqd, dg)
-    for what, f, c, ref in zip(("gq", "gqd"), fused, comp, (rq, rd)):
-        err = float((f - c).abs().max()) / max(1.0, float(np.abs(ref).max()))
-        print("coriolis_vjp %s %s: fused against composition %.3e; composition against the oracle %.3e" % (name, what, err, cases.rel_err(c.cpu().numpy(), ref)))
-        assert err <= 2e-9, (name, what, err)
+    for what, f, c, scale in zip(("gq", "gqd"), fused, comp, _scales(name)):
+        err = float((f - c).abs().max()) / scale
+        print("coriolis_vjp %s %s: fused against composition %.3e (scale %.3g)" % (name, what, err, scale))
+        assert bool(torch.isfinite(f).all()) and err <= 2e-9, (name, what, err)
 
 
 @gpu
@@ -398,22 +435,75 @@ def test_guard_rows_every_row_written_inputs_unchanged(name, N):
 
 
 @gpu
-@pytest.mark.parametrize("name", ["puma560", "n8s", "n9m", "tree7", "UR5", "YuMi"])
+@pytest.mark.parametrize("name", ["puma560", "n8s", "n9m", "tree7", "UR5", "KinovaGen3", "YuMi"])
 def test_rows_are_independent(name):
-    """a row's result does not depend on its tile mates: N = 65 against the same rows one at a time, and a row permutation permutes the results"""
+    """a row's result does not depend on its tile mates: N = 65 DISTINCT rows against rows either side of the 8-, 32- and 64-row seams computed one
+    at a time, and a row permutation permutes the results"""
     torch = _torch()
     N = 65
-    rb, q, qd, g, rq, rd = cases.case(name, N)
+    rb, q, qd, g = _distinct(name, N)
+    assert len({q[r].tobytes() for r in range(N)}) == N
     dq, dqd, dg = _dev(torch, q, qd, g)
     full = _vjp(rb, dq, dqd, dg)
-    for r in range(cases.ROWS):          # (the distinct rows of the case; the others repeat them, and the permutation below covers every row)
+    for r in (0, 1, 7, 8, 9, 31, 32, 62, 63, 64):
         one = _vjp(rb, dq[r:r + 1].contiguous(), dqd[r:r + 1].contiguous(), dg[r:r + 1].contiguous())
-        assert torch.equal(one[0][0], full[0][r]) and torch.equal(one[1][0], full[1][r])
+        assert torch.equal(one[0][0], full[0][r]) and torch.equal(one[1][0], full[1][r]), (name, r)
     perm = np.random.default_rng(5).permutation(N)
     pq, pqd, pg = _dev(torch, q[perm], qd[perm], g[perm])
     moved = _vjp(rb, pq, pqd, pg)
     idx = torch.from_numpy(perm).cuda()
     assert torch.equal(full[0][idx], moved[0]) and torch.equal(full[1][idx], moved[1])
+
+
+@gpu
+@pytest.mark.parametrize("name", ["panda", "n9s", "UR5", "tree9"])
+def test_nonfinite_and_huge_joint_values_stay_in_their_row(name):
+    """a register form and a run-time-n form of each entry point, N = 130 distinct rows (three tiles).  A NaN in q or qd of row 70 makes that row
+    non-finite and no other: the other two tiles keep the BITS of the clean run; the tile mates (rows 64..127) stay finite and within
+    2e-9 max(1, |ref|max) of the composition -- a NaN angle sends its whole wave through the library's sincos (rtb_sincos and tree_trig decide with
+    wave_any), so a mate may differ from the clean run by the difference of the two routines and by nothing else; the run-time-n tree form always
+    calls the library's, so there every row but 70 keeps its bits.  A NaN in gC never reaches the trigonometry: every row but 70 keeps its bits in
+    every form.  One angle of 2^21 + 0.25 rad in row 5: the mates of tile 0 within the same bound, tiles 1 and 2 bit-equal, and row 5 itself at
+    1e-9 max(1, |ref|max) of the oracle evaluated with h = 2^-10 (its own error there:
+    test_the_oracle_is_a_hundred_times_finer_than_the_bound)."""
+    torch = _torch()
+    N, bad, big = 130, 70, 5
+    rb, q, qd, g = _distinct(name, N)
+    run = lambda a, b, c: [x.cpu().numpy() for x in _vjp(rb, *_dev(torch, a, b, c))]
+    clean = run(q, qd, g)
+    comp = [x.cpu().numpy() for x in _composition(rb, *_dev(torch, q, qd, g))]
+    scale = _scales(name)
+    for k in (0, 1):
+        assert np.isfinite(clean[k]).all() and float(np.abs(clean[k] - comp[k]).max()) <= 2e-9 * scale[k]
+    always_library = _is_tree(rb) and rb.n > 8          # csrc/tree_coriolis_vjp_kernels.hip:85-91
+    rows = np.arange(N)
+
+    def check(what, got, row, depends, exact):
+        tile = rows // 64 == row // 64
+        mates, same = tile & (rows != row), (rows != row) if exact else ~tile
+        for k, o in enumerate(("gq", "gqd")):
+            if depends[k]:
+                assert not np.isfinite(got[k][row]).all(), (name, what, o, "row %d is finite" % row)
+            assert _bits(got[k][same], clean[k][same]), (name, what, o, "a row outside the tile differs from the clean run", np.flatnonzero((got[k] != clean[k]).any(axis=1))[:8])
+            assert np.isfinite(got[k][mates]).all(), (name, what, o, "a tile mate is not finite", np.flatnonzero(~np.isfinite(got[k]).all(axis=1))[:8])
+            err = float(np.abs(got[k][mates] - comp[k][mates]).max()) / scale[k]
+            print("coriolis_vjp %s %s %s: tile mates against the composition %.3e" % (name, what, o, err))
+            assert err <= 2e-9, (name, what, o, err)
+
+    a = q.copy(); a[bad, 1] = np.nan
+    check("NaN in q", run(a, qd, g), bad, (True, True), always_library)
+    a = qd.copy(); a[bad, 1] = np.nan
+    check("NaN in qd", run(q, a, g), bad, (True, False), always_library)          # (C is linear in qd: gqd does not depend on it)
+    a = g.copy(); a[bad] = np.nan
+    check("NaN in gC", run(q, qd, a), bad, (True, True), True)
+    a = q.copy(); a[big, 2] = BIG_ANGLE
+    got = run(a, qd, g)
+    check("huge angle", got, big, (False, False), always_library)
+    ref = _oracle(name, a[big:big + 1], qd[big:big + 1], g[big:big + 1], BIG_H)
+    for k, o in enumerate(("gq", "gqd")):
+        err = cases.rel_err(got[k][big:big + 1], ref[k])
+        print("coriolis_vjp %s huge angle %s: row %d against the oracle at h = 2^-10 %.3e (|ref|max %.3g)" % (name, o, big, err, np.abs(ref[k]).max()))
+        assert err <= cases.BOUND, (name, o, err)
 
 
 @gpu

@@ -12,6 +12,11 @@ What a row does, at every N in SIZES (one lane; the 8-configuration line groups 
    file:line pointer): all N rows at every N, for the compiled oracles and for the Python-loop ones alike (oracle/erobot.py, the Richardson
    stencils over it, the momentum balance, the Python IK solvers), each computed once on the 129 rows.  The only rows left out are those the
    family's own test leaves out: a singular J J^T for jacobm_from_jacobian, a sum on the p_servo threshold, an IK target the oracle does not solve.
+   The fused adjoints of the Coriolis matrix of a link tree (and of the inertia matrix of the 9-joint tree) are the exception in cost: their oracle
+   is a Python loop of n + n (n - 1) / 2 inverse-dynamics evaluations per matrix and 5 n matrices per row.  It runs on ORACLE_ROWS_24 / _14 (the
+   seams, every residue mod 8, three classes twice in one tile), and EVERY row is held at 2e-9 max(1, |ref|max) to the composition the fused call
+   replaces -- launches of rtbhip_tree_rne_vjp, another kernel, itself held to its oracle on all 129 rows here -- at N = 129; every smaller N must
+   return the bits of the leading rows of that result (Case.second).  No row of any table row is left out of both.
    Outputs are finite everywhere (a read past the last input row would bring in a NaN of the input guards); IK: wherever it reports success.
 3. row independence.  Every row of SEAM_ROWS below N -- the first row, the last row of every size and the rows either side of every multiple of
    8 -- has the bits of the same row computed alone (N = 1).
@@ -31,6 +36,17 @@ compiler chooses per kernel; each is held to the oracle bound on its own.
 
 Ad-hoc chains are created and run under rtbhip.tune("jit", 0): no case waits for, or leaves behind, a run-time compile.  A fixture restores every
 knob.
+
+The fused adjoints of the inertia and Coriolis matrices (rtbhip_inertia_vjp, rtbhip_coriolis_vjp and their tree forms): the register forms, the
+last register size, the first run-time-n size and a long one of each; for the Coriolis pair gq alone and gqd alone return the bits of the call that
+asks for both and leave the other buffer untouched (Case.same_as).  A tree of at most 8 groups that launch_tree_coriolis_vjp cannot serve with
+the register form exists only with hand numbering: the register form's request 64 * 8 * (((2 n + n^2) | 1) + 24 nslots + 18 nkept) exceeds
+160 KB = 320 doubles per lane only at n = 8 (row 81) with 24 nslots + 18 nkept > 239; nslots <= n - 2 = 6 (a slot needs a parent with a child
+two or more groups on), nkept <= n - 1 = 7.  A depth-first numbering keeps only leaves and has a slot per branching group, at most 162.  _ladder8
+(group j off group j - 2: 6 slots, 7 kept, 179712 bytes) is such a table; its row asserts the run-time-n request, 86528 bytes.
+
+The set of entry points is read from include/rtbhip.h (header_census): every `int rtbhip_*(..., int32_t mem, void *stream)`.  The ctypes table's
+stream types (_sp, _si, _sc, ...) serve the families' refusal censuses and decide nothing here.
 
 Row-independence exceptions: none.  Every entry point of the table, IK included (q0 supplied, one search), returns for a row of a batch the bits
 of that row computed alone.
@@ -56,8 +72,18 @@ fraction of the bound it is held to:
     manipulability                 1.2e-14  (4.8e-04)     link_frames              5.6e-16  (5.6e-06)
     jacobm                         2.4e-14  (1.8e-05)
 
+    inertia_vjp            gq      3.4e-11  (8.1e-04)     tree_inertia_vjp    gq   7.0e-12  (1.9e-03)   against the composition  5.3e-15  (1.2e-07)
+    coriolis_vjp           gq      9.3e-11  (1.4e-03)     tree_coriolis_vjp   gq   1.2e-11  (9.3e-04)   against the composition  3.6e-14  (1.1e-06)
+                           gqd     3.2e-14  (1.6e-06)                         gqd  4.9e-15  (1.6e-06)   against the composition  1.4e-14  (8.5e-07)
+
+(gq is held to a finite-difference stencil whose own error is some 1e-12 of the scale; gqd of the Coriolis pair to the exact linearity in qd, and
+the fused call agrees with the composition it replaces to a few ulp.)
+
 (The float32 rows sit at their bound by construction: it is 1e-9 of the scale plus half a float32 ulp of the value, and the rounding error of a
-float32 result reaches half an ulp.)  The whole module takes 21 s on the device, the slowest row 3.7 s (the Richardson stencil of a 9-joint tree on all 129 rows)."""
+float32 result reaches half an ulp.)  The whole module takes 85 s on the device, 21 s of it the rows that were here before the inertia / Coriolis adjoints joined (slowest of those
+3.7 s, the Richardson stencil of a 9-joint tree on all 129 rows).  The 26 adjoint rows cost 64 s, nearly all of it their CPU oracles, each computed
+once per robot: tree_coriolis_vjp tree8 11.3 s and tree9 10.5 s (the Python Coriolis stencil on 24 / 14 oracle rows, the fewest the row
+conditions allow), coriolis_vjp n12m 8.5 s (600 000 calls of the compiled inverse dynamics), tree_inertia_vjp tree8 7.9 s (all 129 rows)."""
 import functools
 import os
 
@@ -113,11 +139,18 @@ class Case:
     row (an output whose p() is never asked for must stay untouched); ref: output name -> (NMAX, width) oracle rows; rows: None (all rows carry an
     oracle value) | index array | name -> either; tol(name, ref rows, their indices) -> absolute bound per entry; err(name, got, ref) -> deviation per entry
     (default |got - ref|); launch(N) -> (grid, LDS bytes | None); check(res, N): a comparison of its own instead (IK); twin: knobs under which the
-    N = NMAX call must return the same bits; zero_ok: the oracle may be zero everywhere (else that is a vacuous row and fails)"""
+    N = NMAX call must return the same bits; zero_ok: the oracle may be zero everywhere (else that is a vacuous row and fails);
+    second() -> output name -> (NMAX, width): a second reference that has a value on EVERY row (where the oracle is affordable on a few rows only),
+    evaluated once after the N = NMAX call and compared with it on all rows at tol2(name, second rows) -- and then every smaller N must have
+    returned the bits of the leading rows of the N = NMAX result, which ties their rows to that comparison; same_as() -> another Case on the same
+    inputs (the call with every output asked for) whose N = NMAX call must return the same bits for the outputs this one asks for"""
 
-    def __init__(self, fn, ins, outs, args, ref=None, tol=None, rows=None, err=None, launch=None, check=None, twin=None, keep=None, zero_ok=False):
+    def __init__(self, fn, ins, outs, args, ref=None, tol=None, rows=None, err=None, launch=None, check=None, twin=None, keep=None, zero_ok=False,
+                 second=None, tol2=None, same_as=None):
         self.fn, self.ins, self.outs, self.args, self.ref, self.tol, self.rows = fn, ins, outs, args, ref or {}, tol, rows
         self.err, self.launch, self.check, self.twin, self.keep, self.zero_ok = err, launch, check, twin, keep, zero_ok
+        self.second, self.tol2, self.same_as = second, tol2, same_as
+        assert (second is None) == (tol2 is None)
 
     def rows_of(self, name, N):
         r = self.rows.get(name) if isinstance(self.rows, dict) else self.rows
@@ -178,6 +211,24 @@ def _compare(case, rid, res, N):
         assert bool((e <= t).all()), (rid, N, name, "max deviation %.3e, %.3g of its bound, row %d" % (e.max(), ratio.max(), rows[int(np.argmax(ratio.reshape(len(rows), -1).max(axis=1)))]))
 
 
+def _compare_second(case, rid, by_size):
+    """every row of the N = NMAX result against the second reference, then every smaller N against the leading rows of that result, bit for bit"""
+    full = by_size[NMAX]
+    for name, want in case.second().items():
+        got = full[name].astype(np.float64)
+        assert want.shape == got.shape and np.isfinite(want).all(), (rid, name, "the second reference has no value on some row")
+        e = np.abs(got - want)
+        t = np.broadcast_to(np.asarray(case.tol2(name, want), dtype=np.float64), e.shape)
+        ratio = e / np.maximum(t, 1e-300)
+        w = WORST.setdefault(rid, {}).setdefault((case.fn, name + " (second reference, all rows)"), [0.0, 0.0])
+        w[0], w[1] = max(w[0], float(e.max())), max(w[1], float(ratio.max()))
+        assert bool((e <= t).all()), (rid, name, "second reference: max deviation %.3e, %.3g of its bound, row %d" % (
+            e.max(), ratio.max(), int(np.argmax(ratio.reshape(NMAX, -1).max(axis=1)))))
+    for N, res in by_size.items():
+        for name, got in res.items():
+            assert _same_bits(got, full[name][:N]), (rid, N, name, "differs from the leading rows of the N = %d result" % NMAX)
+
+
 ROWS = []          # (id, entry point, knobs, builder of the Case)
 
 
@@ -198,8 +249,10 @@ def _run_row(rid, fn, knobs, build):
     case = build()
     assert case.fn == fn
     alone = {int(r): _call(torch, case, np.array([r]), (rid, "row %d alone" % r))[0] for r in SEAM_ROWS}
+    by_size = {}
     for N in SIZES:
         res, launch = _call(torch, case, np.arange(N), (rid, N))
+        by_size[N] = res
         if case.launch is not None and not replaying():
             grid, lds = case.launch(N)
             assert launch[0] == grid and launch[1] == 64, (rid, N, "launch", launch, "expected grid", grid)
@@ -222,6 +275,12 @@ def _run_row(rid, fn, knobs, build):
                 rtbhip.tune(k, v)
             for name in res:
                 assert _same_bits(res[name], other[name]), (rid, name, "bits differ under", case.twin)
+        if N == NMAX and case.same_as is not None:
+            other, _ = _call(torch, case.same_as(), np.arange(N), (rid, N, "every output asked for"))
+            for name in res:
+                assert _same_bits(res[name], other[name]), (rid, name, "bits differ from the call with every output asked for")
+    if case.second is not None:
+        _compare_second(case, rid, by_size)
     for (f, name), (e, ratio) in sorted(WORST.get(rid, {}).items()):
         print("flush_guard_all %s: %s %s max deviation %.3e (%.3g of its bound)" % (rid, f, name, e, ratio))
 
@@ -885,6 +944,227 @@ for _r in ("panda", "panda_base", "n6", "n9", "n12", "cols"):
     row("link_frames_vjp %s" % _r, "rtbhip_link_frames_vjp", {} if _r.startswith("panda") else JIT0, _link_frames_vjp(_r))
 
 
+# ------------------------------------------------------------------------------------------------ the adjoints of the inertia and Coriolis matrices
+# Inputs as tests/inertia_vjp_cases.py:54-60 and tests/coriolis_vjp_cases.py:58-64 draw them -- q ~ U(-3, 3), qd ~ U(-2, 2), gM / gC ~ U(-1, 1), NOT
+# symmetric -- but NMAX DISTINCT rows, drawn once per robot: the family's own cases repeat 8 (or 2) rows cyclically, and a staging or flush error
+# that moves a row by a multiple of that period returns exactly the expected bits there.
+CSUBSETS = {"both": (True, True), "gq": (True, False), "gqd": (False, True)}          # tests/test_coriolis_vjp.py:334-337
+# The rows on which the Python-loop oracle of the tree Coriolis adjoint runs (n + n (n - 1) / 2 inverse-dynamics evaluations per matrix, 5 n matrices
+# per row): the first and last row, both sides of the 8-row and 64-row seams, every residue class mod 8, and three classes (0, 7, 1) with two rows
+# in one tile.  Every row, these included, is ALSO held to the composition the fused call replaces (Case.second).
+ORACLE_ROWS_14 = np.array([0, 2, 7, 8, 11, 20, 29, 38, 63, 64, 65, 73, 127, 128])
+ORACLE_ROWS_24 = np.array(sorted(set(ORACLE_ROWS_14.tolist()) | {16, 33, 47, 48, 70, 86, 95, 100, 109, 118}))
+for _rows, _least in ((ORACLE_ROWS_14, 12), (ORACLE_ROWS_24, 24)):
+    assert len(_rows) >= _least and len(set(_rows.tolist())) == len(_rows) and _rows.max() < NMAX
+    assert {0, 7, 8, 63, 64, 65, 127, 128} <= set(_rows.tolist()) and {int(r) % 8 for r in _rows} == set(range(8))
+    _pairs = {(int(r) % 8, int(r) // 64) for r in _rows if sum(1 for x in _rows if x % 8 == r % 8 and x // 64 == r // 64) >= 2}
+    assert len({c for c, _ in _pairs}) >= 3, _pairs
+
+
+@functools.lru_cache(maxsize=None)
+def _mat_vjp_inputs(kind, name, n):
+    rng = _rng(kind, name)
+    return rng.uniform(-3, 3, (NMAX, n)), rng.uniform(-2, 2, (NMAX, n)), rng.uniform(-1, 1, (NMAX, n, n))
+
+
+def _tree_slots_kept(parents):
+    """(branch slots, kept groups) of a group table, restated: a group whose parent is not the group in front of it reads the parent's state through a
+    slot, one slot per such parent (csrc/tree.cpp:94-101); the adjoint keeps the state of group j unless group j + 1 hangs directly off it
+    (csrc/tree_coriolis_vjp_kernels.hip:97, 466-468)"""
+    n = len(parents)
+    return len({p for j, p in enumerate(parents) if p >= 0 and p != j - 1}), sum(1 for j in range(n) if j + 1 >= n or parents[j + 1] != j)
+
+
+def _tree_coriolis_vjp_lds(n, nslots, nkept, rt):
+    """csrc/tree_coriolis_vjp_kernels.hip:328, 469-471: q | qd | gC (one row of it in the run-time-n form) at an odd stride, 24 doubles per branch
+    slot, and in the register form 18 per kept group"""
+    return 64 * 8 * (((2 * n + (n if rt else n * n)) | 1) + 24 * nslots + (0 if rt else 18 * nkept))
+
+
+@functools.lru_cache(maxsize=None)
+def _ladder8():
+    """(ERobot, the oracle's link list): 8 groups, group j hanging off group j - 2 (group 1 off group 0), numbered by hand IN group order, which
+    keeps the links in the order given (a depth-first numbering cannot produce this table: there a group that does not hang off the one in front of
+    it follows a leaf).  6 branch slots and 7 kept groups: the register form of rtbhip_tree_coriolis_vjp would ask for
+    64 * 8 * (81 + 24 * 6 + 18 * 7) = 179712 bytes > 160 KB, so launch_tree_coriolis_vjp serves it with the run-time-n form,
+    64 * 8 * (25 + 24 * 6) = 86528 bytes (csrc/tree_coriolis_vjp_kernels.hip:472).  One prismatic and one flipped joint."""
+    from rtbhip import ET, ETS, Link, ERobot
+    rng = _rng("ladder8")
+    axes, flips = ("Rz", "Ry", "Rx", "tz", "Rz", "Ry", "Rx", "Rz"), (False, False, True, False, False, False, True, False)
+    prod, orc = [], []
+    for i, (a, fl) in enumerate(zip(axes, flips)):
+        parent = None if i == 0 else max(0, i - 2)
+        T = chains.elementary("Rz", rng.uniform(-1, 1)) @ chains.elementary("tx", rng.uniform(-.3, .3)) @ chains.elementary("Rx", rng.uniform(-1, 1))
+        m, r = float(rng.uniform(0.5, 3)), rng.uniform(-0.3, 0.3, 3)
+        prod.append(Link(ets=ETS() * ET.SE3(T) * getattr(ET, a)(flip=fl), jindex=i, m=m, r=r, parent=None if parent is None else prod[parent], name="d%d" % i))
+        orc.append(dict(name="d%d" % i, parent=None if parent is None else "d%d" % parent, ets=[T, (a, None, fl)], m=m, r=r, jindex=i))
+    rob = ERobot(prod, name="ladder8")
+    parents = [r["parent"] for r in rob.group_table()]
+    assert rob.n == 8 and rob._in_group_order() and parents == [-1, 0, 0, 1, 2, 3, 4, 5] and _tree_slots_kept(parents) == (6, 7)
+    return rob, orc
+
+
+# Which trees of at most 8 groups the register form cannot serve: 64 * 8 * (((2 n + n^2) | 1) + 24 nslots + 18 nkept) > 160 * 1024 means more than
+# 320 doubles per lane; at n = 8 the row is 81, so 24 nslots + 18 nkept > 239.  A slot needs a parent p with a child j >= p + 2, so nslots <= n - 2 = 6;
+# nkept <= n - 1 = 7 with one base link (group 1 hangs off group 0).  (6, 7) gives 270 and (5, 7) 246: both over, (4, 7) 222 is not; n = 7 has a row of
+# (14 + 49) | 1 = 63 doubles, at most 5 slots and 6 kept groups: 291 <= 320, the register form.  So only 8-group tables numbered by hand reach the fallback -- _ladder8 is one.
+assert _tree_coriolis_vjp_lds(8, 6, 7, False) == 179712 > 160 * 1024 >= _tree_coriolis_vjp_lds(7, 5, 6, False) and _tree_coriolis_vjp_lds(8, 6, 7, True) == 86528
+assert _tree_coriolis_vjp_lds(8, 5, 7, False) > 160 * 1024 >= _tree_coriolis_vjp_lds(8, 4, 7, False)
+
+
+def _mtree(name):
+    return _ladder8() if name == "ladder8" else _tree(name)
+
+
+MAT_DH_KN = lambda name: {} if name in ("puma560", "panda") else JIT0
+MAT_TREE_KN = lambda name: {} if name == "UR5" else JIT0
+
+
+def _mat_dh_robot(name):
+    import inertia_vjp_cases as ic
+    return ic.dh_robot(name)          # puma560, panda and the random all-revolute tables nNs / nNm of tests/rne_vjp_cases.py, N up to 16
+
+
+@functools.lru_cache(maxsize=None)
+def _inertia_vjp_ref(name, tree):
+    """tests/inertia_vjp_cases.py:63-74: five-point Richardson differences, h = 1e-3 (tests/rne_vjp_cases.py:20, 66-76), of the reference's inertia
+    matrix, one q column at a time, contracted with gM -- on every one of the NMAX rows, once per robot"""
+    import inertia_vjp_cases as ic
+    if tree:
+        rob, orc = _mtree(name)
+        q, _, g = _mat_vjp_inputs("tree inertia vjp", name, rob.n)
+        r = _inertia_oracle_rows(name)
+        return ic.tree_oracle(orc, q, g) if r is None else _sparse(r, ic.tree_oracle(orc, q[r], g[r]))
+    rb = _mat_dh_robot(name)
+    q, _, g = _mat_vjp_inputs("inertia vjp", name, rb.n)
+    return ic.dh_oracle(rb, q, g)
+
+
+def _inertia_oracle_rows(name):
+    """every row (None) -- but the stencil of the 9-joint tree on 129 rows is 42 000 evaluations of the Python inverse dynamics, three times the
+    slowest row this table had: tree9 takes the oracle rows and the composition on every row, as the tree Coriolis rows below do"""
+    return ORACLE_ROWS_14 if name == "tree9" else None
+
+
+@functools.lru_cache(maxsize=None)
+def _tree_inertia_composition(name):
+    """tests/test_inertia_vjp.py:262-280 (_composition): what the fused call replaces -- n launches of rtbhip_tree_rne_vjp at qd = 0, qdd = e_i,
+    gtau = gM[:, i, :], no gravity, summed -- on all NMAX rows"""
+    import torch
+    from test_inertia_vjp import _composition
+    rob, _ = _mtree(name)
+    q, _, g = _mat_vjp_inputs("tree inertia vjp", name, rob.n)
+    return _composition(rob, *(torch.from_numpy(np.ascontiguousarray(x)).to(DEV()) for x in (q, g))).cpu().numpy()
+
+
+def _inertia_vjp(name, tree):
+    """tests/test_inertia_vjp.py:319-328: the oracle above, bound 1e-9 max(1, |ref|max) (tests/inertia_vjp_cases.py:13; VJP_TOL); where the
+    oracle runs on the oracle rows only, every row is also within 2e-9 max(1, |ref|max) of the composition (tests/test_inertia_vjp.py:333-344)"""
+    def build():
+        rows, second, tol2 = None, None, None
+        ref = _inertia_vjp_ref(name, tree)
+        if tree:
+            rob, _ = _mtree(name)
+            n, h, fn, launch = rob.n, rob._handle(), "rtbhip_tree_inertia_vjp", _grid_only          # (its LDS request counts the robot's branch slots)
+            q, _, g = _mat_vjp_inputs("tree inertia vjp", name, n)
+            rows = _inertia_oracle_rows(name)
+            if rows is not None:
+                scale = max(1.0, float(np.abs(ref[rows]).max()))
+                second, tol2 = (lambda: {"gq": _tree_inertia_composition(name)}), (lambda nm, w: 2e-9 * scale)
+        else:
+            rob = _mat_dh_robot(name)
+            n, h, fn = rob.n, rob._dyn_handle(), "rtbhip_inertia_vjp"
+            q, _, g = _mat_vjp_inputs("inertia vjp", name, n)
+            # csrc/inertia_vjp_kernels.hip:186, 328: q (n) | the folded gM (n (n + 1) / 2) at an odd stride, the register and the run-time-n form alike
+            launch = lambda N: (_tiles(N), 64 * 8 * ((n + n * (n + 1) // 2) | 1))
+        return Case(fn, {"q": In(q), "gM": In(g)}, [O("gq", n)], lambda N, p, s: (h, p("q"), N, p("gM"), p("gq"), MEM, s),
+                    ref={"gq": ref}, rows=rows, tol=VJP_TOL, launch=launch, keep=rob, second=second, tol2=tol2)
+    return build
+
+
+for _r in ("puma560", "panda", "n8s", "n9s", "n16m"):          # 6 standard DH, 7 modified DH; 8: the last register size; 9: the first run-time-n size; 16: the limit
+    row("inertia_vjp %s" % _r, "rtbhip_inertia_vjp", MAT_DH_KN(_r), _inertia_vjp(_r, False))
+for _r in ("UR5", "tree7", "tree8", "tree9"):                  # tree7: branch slots in use; tree8: the last register size; tree9: run-time-n
+    row("tree_inertia_vjp %s" % _r, "rtbhip_tree_inertia_vjp", MAT_TREE_KN(_r), _inertia_vjp(_r, True))
+
+
+def _coriolis_oracle_rows(name):
+    return ORACLE_ROWS_14 if name in ("tree9", "ladder8") else ORACLE_ROWS_24          # (the two that the run-time-n form serves)
+
+
+@functools.lru_cache(maxsize=None)
+def _coriolis_vjp_ref(name, tree):
+    """tests/coriolis_vjp_cases.py:67-102: gq by the same stencil, h = 1e-3, on the reference's Coriolis matrix; gqd exactly, from the linearity of C
+    in qd (gqd[:, m] = sum_jk gC[:, j, k] C(q, e_m)[:, j, k]).  DH: the compiled reference, all NMAX rows.  Trees: the Python loop, on the robot's
+    oracle rows only -> (gq, gqd) as (NMAX, n) with NaN on the other rows"""
+    import coriolis_vjp_cases as cc
+    if tree:
+        rob, orc = _mtree(name)
+        q, qd, g = _mat_vjp_inputs("tree coriolis vjp", name, rob.n)
+        r = _coriolis_oracle_rows(name)
+        return tuple(_sparse(r, x) for x in cc.tree_oracle(orc, q[r], qd[r], g[r]))
+    rb = _mat_dh_robot(name)
+    q, qd, g = _mat_vjp_inputs("coriolis vjp", name, rb.n)
+    return cc.dh_oracle(rb, q, qd, g)
+
+
+@functools.lru_cache(maxsize=None)
+def _tree_coriolis_composition(name):
+    """tests/test_coriolis_vjp.py:272-291 (_composition): what the fused call replaces -- 2 n launches of rtbhip_tree_rne_vjp at qd +- e_k with
+    gtau = +-1/4 gC[:, :, k], summed -- on all NMAX rows, once per robot.  rtbhip_tree_rne_vjp is another kernel, held to the oracle on all 129
+    distinct rows by the tree_rne_vjp rows above."""
+    import torch
+    from test_coriolis_vjp import _composition
+    rob, _ = _mtree(name)
+    dq, dqd, dg = (torch.from_numpy(np.ascontiguousarray(x)).to(DEV()) for x in _mat_vjp_inputs("tree coriolis vjp", name, rob.n))
+    return tuple(x.cpu().numpy() for x in _composition(rob, dq, dqd, dg))
+
+
+def _coriolis_vjp(name, subset, tree, lds=None):
+    """tests/test_coriolis_vjp.py:321-337: both gradients at 1e-9 max(1, |ref|max) (VJP_TOL); gq alone and gqd alone return the bits of the call
+    that asks for both (Case.same_as) and leave the other buffer alone.  Trees: the oracle on the oracle rows, and EVERY row within
+    2e-9 max(1, |ref|max) of the composition (tests/test_coriolis_vjp.py:342-352: each side is within 1e-9 of the oracle; the scale is the
+    oracle rows')"""
+    def build():
+        want = CSUBSETS[subset]
+        names = [k for k, w in zip(("gq", "gqd"), want) if w]
+        if tree:
+            rob, _ = _mtree(name)
+            n, h, fn = rob.n, rob._handle(), "rtbhip_tree_coriolis_vjp"
+            q, qd, g = _mat_vjp_inputs("tree coriolis vjp", name, n)
+            rows = _coriolis_oracle_rows(name)
+            launch = _grid_only if lds is None else (lambda N: (_tiles(N), lds))
+            ref = dict(zip(("gq", "gqd"), _coriolis_vjp_ref(name, True)))
+            scale = {k: max(1.0, float(np.abs(ref[k][rows]).max())) for k in names}
+            second = lambda: {k: v for k, v in zip(("gq", "gqd"), _tree_coriolis_composition(name)) if k in names}
+            tol2 = lambda nm, w: 2e-9 * scale[nm]
+        else:
+            rob = _mat_dh_robot(name)
+            n, h, fn = rob.n, rob._dyn_handle(), "rtbhip_coriolis_vjp"
+            q, qd, g = _mat_vjp_inputs("coriolis vjp", name, n)
+            rows, second, tol2 = None, None, None
+            rt = n > 7          # csrc/coriolis_vjp_kernels.hip:246, 255, 399-400: q | qd | gC at an odd stride; beyond kCoriolisVjpRegMax one row of gC per pass
+            launch = lambda N: (_tiles(N), 64 * 8 * ((2 * n + (n if rt else n * n)) | 1))
+            ref = dict(zip(("gq", "gqd"), _coriolis_vjp_ref(name, False)))
+        return Case(fn, {"q": In(q), "qd": In(qd), "gC": In(g)}, [O("gq", n), O("gqd", n)],
+                    lambda N, p, s: (h, p("q"), p("qd"), N, p("gC")) + tuple(p(k) if w else None for k, w in zip(("gq", "gqd"), want)) + (MEM, s),
+                    ref={k: ref[k] for k in names}, rows=rows, tol=VJP_TOL, launch=launch, keep=rob, second=second, tol2=tol2,
+                    same_as=None if subset == "both" else _coriolis_vjp(name, "both", tree, lds))
+    return build
+
+
+# 6 and 7 = kCoriolisVjpRegMax: the register forms; 8: the first run-time-n size; 12: run-time-n with a longer pass loop.  (The limit size, 16, is
+# 1.4e6 inverse-dynamics calls of the compiled reference on 129 rows -- half a minute; it runs in tests/test_coriolis_vjp.py.)
+for _r in ("puma560", "panda", "n8m", "n12m"):
+    for _s in CSUBSETS if _r in ("panda", "n8m") else ("both",):
+        row("coriolis_vjp %s %s" % (_r, _s), "rtbhip_coriolis_vjp", MAT_DH_KN(_r), _coriolis_vjp(_r, _s, False))
+for _r in ("UR5", "tree7", "tree8", "tree9"):
+    for _s in CSUBSETS if _r in ("UR5", "tree9") else ("both",):
+        row("tree_coriolis_vjp %s %s" % (_r, _s), "rtbhip_tree_coriolis_vjp", MAT_TREE_KN(_r), _coriolis_vjp(_r, _s, True))
+# 8 groups whose register-form request does not fit a CU's LDS: the run-time-n form at n = 8, its request asserted (see _ladder8)
+row("tree_coriolis_vjp ladder8 both", "rtbhip_tree_coriolis_vjp", JIT0, _coriolis_vjp("ladder8", "both", True, lds=_tree_coriolis_vjp_lds(8, 6, 7, True)))
+
+
 # ------------------------------------------------------------------------------------------------ the tests
 # entry points whose flush already has guard rows (or poisoned buffers) around every output, every row against the oracle: entry point -> that test
 ELSEWHERE = dict([(n, "test_kin_flush_guard_gpu.py::test_flush_writes_its_rows_and_leaves_the_guard_rows") for n in (
@@ -893,21 +1173,50 @@ ELSEWHERE = dict([(n, "test_kin_flush_guard_gpu.py::test_flush_writes_its_rows_a
     ("rtbhip_partial_fkine0", "test_partial_fkine0.py::test_gpu_writes_its_rows_and_nothing_else")])
 
 
+NOT_COMPUTE = ("rtbhip_device_copy", "rtbhip_ik_restart")          # (..., mem / kind, stream) by shape, but no batch of rows is computed
+
+
+def header_census():
+    """every compute entry point, from include/rtbhip.h itself: each `int rtbhip_*(` declaration whose parameter list ends in
+    `int32_t mem, void *stream)`.  The ctypes table cannot opt an entry point out of this one by the type it gives the stream argument."""
+    import re
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rtbhip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    found = set()
+    for name, params in re.findall(r"\bint\s+(rtbhip_\w+)\s*\(([^;{}]*?)\)\s*;", hdr, flags=re.S):
+        if re.search(r"\bint32_t\s+mem\s*,\s*void\s*\*\s*stream\s*$", " ".join(params.split())):
+            found.add(name)
+    return found - set(NOT_COMPUTE)
+
+
 def census():
-    """every compute entry point of include/rtbhip.h: (..., mem, stream) by shape as tests/test_api_refusals.py:924 builds the set, plus the
-    vector-Jacobian products, whose stream argument is _lib._sp (tests/test_kin_vjp.py:97) or one of its subclasses (_sq, _st, _sf: rne, tree, frames)"""
+    """the rule by the types of rtbhip/_lib.py: (..., mem, stream) by shape as tests/test_api_refusals.py:924 builds the set, plus the vector-Jacobian
+    products -- by the name, as include/rtbhip.h declares them; the stream types (_lib._sp and its subclasses _sq, _st, _sf; _si and _sc, which
+    are none) claim rows for the families' own refusal censuses and decide nothing here"""
     S = _lib.SIGNATURES
-    compute = {n for n, (_, a) in S.items() if len(a) >= 2 and a[-1] == _lib._vp and a[-2] == _lib._i32 and n not in ("rtbhip_device_copy", "rtbhip_ik_restart")}
-    vjp = {n for n, (_, a) in S.items() if a and (a[-1] is _lib._sp or (isinstance(a[-1], type) and issubclass(a[-1], _lib._sp)))}
+    compute = {n for n, (_, a) in S.items() if len(a) >= 2 and a[-1] == _lib._vp and a[-2] == _lib._i32 and n not in NOT_COMPUTE}
+    vjp = {n for n in header_census() if "_vjp" in n}
     return compute, vjp
+
+
+def types_census():
+    """what the census of this module found before it read the header: the shape rule, and the stream types _sp and its subclasses"""
+    S = _lib.SIGNATURES
+    compute = {n for n, (_, a) in S.items() if len(a) >= 2 and a[-1] == _lib._vp and a[-2] == _lib._i32 and n not in NOT_COMPUTE}
+    return compute | {n for n, (_, a) in S.items() if a and (a[-1] is _lib._sp or (isinstance(a[-1], type) and issubclass(a[-1], _lib._sp)))}
 
 
 def test_every_compute_entry_point_is_in_the_table_or_guard_checked_elsewhere():
     compute, vjp = census()
-    assert len(compute) >= 35 and len(vjp) >= 7, (sorted(compute), sorted(vjp))
+    assert len(compute) >= 35 and len(vjp) >= 11, (sorted(compute), sorted(vjp))
     tabled = {fn for _, fn, _, _ in ROWS}
     assert not tabled & set(ELSEWHERE)
-    assert compute | vjp == tabled | set(ELSEWHERE), sorted((compute | vjp) ^ (tabled | set(ELSEWHERE)))
+    declared = header_census()
+    assert declared == tabled | set(ELSEWHERE), sorted(declared ^ (tabled | set(ELSEWHERE)))
+    assert declared >= types_census() and declared >= compute | vjp, sorted((types_census() | compute | vjp) - declared)
+    assert declared <= set(_lib.SIGNATURES), sorted(declared - set(_lib.SIGNATURES))
+    assert {"rtbhip_inertia_vjp", "rtbhip_tree_inertia_vjp", "rtbhip_coriolis_vjp", "rtbhip_tree_coriolis_vjp"} <= tabled
     here = os.path.dirname(os.path.abspath(__file__))
     for fn, where in ELSEWHERE.items():
         path, test = where.split("::")

@@ -114,7 +114,8 @@ def test_the_rows_name_both_entry_points():
 # ------------------------------------------------------------------------------------------------ the oracle's own error (no GPU)
 @pytest.mark.parametrize("name", ["puma560", "panda", "UR5"])
 def test_the_oracle_is_a_hundred_times_finer_than_the_bound(name):
-    """the stencil at h against h / 2: <= 1e-11 max(1, |ref|max), a hundredth of the bound the adjoint is held to"""
+    """the stencil at h against h / 2: <= 1e-11 max(1, |ref|max), a hundredth of the bound the adjoint is held to; panda and UR5 also with one
+    joint at 2^21 + 0.25 rad, h = 2^-10 against h / 2"""
     if name == "UR5":
         rob, orc, q, g, a = cases.tree_case(name)
         b = cases.tree_oracle(orc, q, g, h=cases.H / 2)
@@ -124,6 +125,25 @@ def test_the_oracle_is_a_hundred_times_finer_than_the_bound(name):
     err = float(np.abs(a - b).max()) / max(1.0, float(np.abs(a).max()))
     print("inertia oracle %s: h against h/2 %.3e (|ref|max %.3g)" % (name, err, np.abs(a).max()))
     assert err <= 1e-11
+    if name in ("panda", "UR5"):
+        # one joint at 2^21 + 0.25 rad, the stencil at h = 2^-10 against h / 2: the reference can supply the number that
+        # test_nonfinite_and_huge_joint_values_stay_in_their_row compares that row with
+        q, g = (np.array(x) for x in cases.draw(q.shape[1], 2, 5))
+        q[:, 2] = BIG_ANGLE
+        a, b = _oracle(name, q, g, BIG_H), _oracle(name, q, g, BIG_H / 2)
+        err = float(np.abs(a - b).max()) / max(1.0, float(np.abs(a).max()))
+        print("inertia oracle %s at a huge angle: h = 2^-10 against h/2 %.3e (|ref|max %.3g)" % (name, err, np.abs(a).max()))
+        assert err <= 1e-11
+
+
+BIG_ANGLE = 2.0 ** 21 + 0.25          # beyond 2^20: the wave of such a lane takes the library's sine and cosine (csrc/inertia_vjp_kernels.hip:48, tree_trig)
+BIG_H = 2.0 ** -10                    # q +- h and q +- 2 h are exact doubles at that magnitude (one ulp is 2^-31); at h = 1e-3 they are not, six digits lost
+
+
+def _oracle(name, q, g, h):
+    if name in cases.DH_ROBOTS:
+        return cases.dh_oracle(cases.dh_robot(name), q, g, h=h)
+    return cases.tree_oracle(cases.tree_robot(name)[1], q, g, h=h)
 
 
 # ------------------------------------------------------------------------------------------------ front-end routing (no GPU)
@@ -272,6 +292,23 @@ def _case(name, N):
     return rob, cases.tiled(q, N), cases.tiled(g, N), cases.tiled(ref, N)
 
 
+def _distinct(name, N):
+    """(robot, q, gM) of N DISTINCT rows from the cases' input distribution, no oracle: for comparisons of bits and of one device result with
+    another.  (A tree case repeats 8 rows, and there a row that lands a multiple of 8 away still meets its expected bits.)"""
+    rb = cases.dh_robot(name) if name in cases.DH_ROBOTS else cases.tree_robot(name)[0]
+    return (rb,) + tuple(np.array(x) for x in cases.draw(rb.n, N, cases._seed(name, N) + 1))
+
+
+def _scale(name):
+    """max(1, |ref|max) from the cached oracle rows of the same robot and the same input distribution"""
+    ref = cases.dh_case(name, 65)[3] if name in cases.DH_ROBOTS else cases.tree_case(name)[4]
+    return max(1.0, float(np.abs(ref).max()))
+
+
+def _bits(a, b):
+    return a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
 SIZES = (1, 63, 64, 65, 130)
 ALL = sorted(cases.DH_ROBOTS) + cases.TREES
 BIG = set(cases.DH_BIG) | set(cases.TREE_BIG)              # 9 joints and more: the run-time-n kernels, at N = 65 only
@@ -298,13 +335,13 @@ def test_fused_call_equals_the_composition(name):
     (The fused kernel is the specialised form: its passes skip the exact zeros of a robot at rest, start at link i and read the folded gM, so
     the two differ by rounding, not only by the order of the n - 1 adds.)"""
     torch = _torch()
-    rb, q, g, ref = _case(name, 65)
+    rb, q, g = _distinct(name, 65)          # 65 distinct rows; the scale is the cached oracle rows'
     dq, dg = _dev(torch, q, g)
     fused, comp = _vjp(rb, dq, dg).cpu().numpy(), _composition(rb, dq, dg).cpu().numpy()
-    scale = max(1.0, float(np.abs(ref).max()))
+    scale = _scale(name)
     err = float(np.abs(fused - comp).max()) / scale
-    print("inertia_vjp %s: fused against composition %.3e; composition against the oracle %.3e" % (name, err, cases.rel_err(comp, ref)))
-    assert err <= 2e-9, (name, err)
+    print("inertia_vjp %s: fused against composition %.3e (scale %.3g)" % (name, err, scale))
+    assert np.isfinite(fused).all() and err <= 2e-9, (name, err)
 
 
 @gpu
@@ -359,15 +396,65 @@ def test_guard_rows_every_row_written_inputs_unchanged(name, N):
 
 
 @gpu
-@pytest.mark.parametrize("name", ["puma560", "n8s", "n9m", "tree7", "UR5", "YuMi"])
+@pytest.mark.parametrize("name", ["puma560", "n8s", "n9m", "tree7", "UR5", "KinovaGen3", "YuMi"])
 def test_rows_are_independent(name):
-    """a row permutation of the inputs permutes gq bit for bit"""
+    """N = 65 DISTINCT rows: rows either side of the 8-, 32- and 64-row seams have the bits of the same row computed alone, and a row permutation
+    of the inputs permutes gq bit for bit"""
     torch = _torch()
-    N = 130
-    rb, q, g, ref = _case(name, N)
+    N = 65
+    rb, q, g = _distinct(name, N)
+    assert len({q[r].tobytes() for r in range(N)}) == N
     perm = np.random.default_rng(5).permutation(N)
     dq, dg, pq, pg = _dev(torch, q, g, q[perm], g[perm])
-    assert torch.equal(_vjp(rb, dq, dg)[torch.from_numpy(perm).cuda()], _vjp(rb, pq, pg))
+    full = _vjp(rb, dq, dg)
+    for r in (0, 1, 7, 8, 9, 31, 32, 62, 63, 64):
+        assert torch.equal(_vjp(rb, dq[r:r + 1].contiguous(), dg[r:r + 1].contiguous())[0], full[r]), (name, r)
+    assert torch.equal(full[torch.from_numpy(perm).cuda()], _vjp(rb, pq, pg))
+
+
+@gpu
+@pytest.mark.parametrize("name", ["panda", "n9s", "UR5", "tree9"])
+def test_nonfinite_and_huge_joint_values_stay_in_their_row(name):
+    """a register form and a run-time-n form of each entry point, N = 130 distinct rows (three tiles).  A NaN in q of row 70 makes that row
+    non-finite and no other: the other two tiles keep the BITS of the clean run; the tile mates (rows 64..127) stay finite and within
+    2e-9 max(1, |ref|max) of the composition -- a NaN angle sends its whole wave through the library's sincos (rtb_sincos and tree_trig decide with
+    wave_any), so a mate may differ from the clean run by the difference of the two routines and by nothing else; the run-time-n tree form always
+    calls the library's, so there every row but 70 keeps its bits.  A NaN in gM never reaches the trigonometry: every row but 70 keeps its bits in
+    every form.  One angle of 2^21 + 0.25 rad in row 5: the mates of tile 0 within the same bound, tiles 1 and 2 bit-equal, and row 5 itself at
+    1e-9 max(1, |ref|max) of the oracle evaluated with h = 2^-10 (its own error there: test_the_oracle_is_a_hundred_times_finer_than_the_bound)."""
+    torch = _torch()
+    N, bad, big = 130, 70, 5
+    rb, q, g = _distinct(name, N)
+    run = lambda a, b: _vjp(rb, *_dev(torch, a, b)).cpu().numpy()
+    clean = run(q, g)
+    comp = _composition(rb, *_dev(torch, q, g)).cpu().numpy()
+    scale = _scale(name)
+    assert np.isfinite(clean).all() and float(np.abs(clean - comp).max()) <= 2e-9 * scale
+    always_library = _is_tree(rb) and rb.n > 8          # csrc/tree_inertia_vjp_kernels.hip:57-63
+    rows = np.arange(N)
+
+    def check(what, got, row, depends, exact):
+        tile = rows // 64 == row // 64
+        mates, same = tile & (rows != row), (rows != row) if exact else ~tile
+        if depends:
+            assert not np.isfinite(got[row]).all(), (name, what, "row %d is finite" % row)
+        assert _bits(got[same], clean[same]), (name, what, "a row outside the tile differs from the clean run", np.flatnonzero((got != clean).any(axis=1))[:8])
+        assert np.isfinite(got[mates]).all(), (name, what, "a tile mate is not finite", np.flatnonzero(~np.isfinite(got).all(axis=1))[:8])
+        err = float(np.abs(got[mates] - comp[mates]).max()) / scale
+        print("inertia_vjp %s %s: tile mates against the composition %.3e" % (name, what, err))
+        assert err <= 2e-9, (name, what, err)
+
+    a = q.copy(); a[bad, 1] = np.nan
+    check("NaN in q", run(a, g), bad, True, always_library)
+    a = g.copy(); a[bad] = np.nan
+    check("NaN in gM", run(q, a), bad, True, True)
+    a = q.copy(); a[big, 2] = BIG_ANGLE
+    got = run(a, g)
+    check("huge angle", got, big, False, always_library)
+    ref = _oracle(name, a[big:big + 1], g[big:big + 1], BIG_H)
+    err = cases.rel_err(got[big:big + 1], ref)
+    print("inertia_vjp %s huge angle: row %d against the oracle at h = 2^-10 %.3e (|ref|max %.3g)" % (name, big, err, np.abs(ref).max()))
+    assert err <= cases.BOUND, (name, err)
 
 
 @gpu
