@@ -38,20 +38,13 @@
 // q | qd | one row of gC, which every lane stages from memory at the head of each pass.  gq and gqd overwrite the q and qd slots and leave as
 // contiguous non-temporal stores.
 #include "dyn_device.h"
+#include "vjp_tile.h"
 
 namespace rtbhip {
 
 #pragma clang fp contract(off)      // every operation as written, as rne_vjp_kernels.hip
 
-RTB_HD double cvz(V3 a, V3 b) { return __builtin_fma(a.x, b.y, -(a.y * b.x)); }       // (a x b).z
 RTB_HD V3 cv_sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-RTB_HD V3 cv_zrate_cross(double s, V3 v) { return v3(-(s * v.y), s * v.x, 0.0); }      // (0, 0, s) x v
-template <class LinkT>
-RTB_HD V3 cv_inertia_t_times(const LinkT &l, V3 v)      // the transpose of inertia_times
-{
-    return v3(__builtin_fma(l.I[2], v.z, __builtin_fma(l.I[1], v.y, l.I[0] * v.x)), __builtin_fma(l.I[5], v.z, __builtin_fma(l.I[4], v.y, l.I[3] * v.x)),
-              __builtin_fma(l.I[8], v.z, __builtin_fma(l.I[7], v.y, l.I[6] * v.x)));
-}
 
 // One sample.  links: the wave-uniform link table, every link revolute.  qin(l), qdin(l): the joint angles and rates; q is read up front, qd stays
 // readable until the last pass is over.  begin(j): called at the head of pass j (the run-time-n kernel stages row j of gC there).  gin(j, l):
@@ -146,8 +139,8 @@ RTB_HD void coriolis_vjp_lane(LinksP links, int n_rt, InQ qin, InQd qdin, Begin 
                     if (MDH) fnb = cross_add(nb, link_offset<MDH>(l1, l1.d), fnb);
                     const V3 f1 = Fq[j + 1], n1 = Nq[j + 1];
                     const V3 fb1 = rot_inv<MDH>(R1, fnb), nb1 = rot_inv<MDH>(R1, nb);
-                    if (MDH) accq[j + 1] = accq[j + 1] + (cvz(f1, fb1) + cvz(n1, nb1));
-                    else accq[j + 1] = accq[j + 1] + (cvz(rot_fwd<MDH>(R1, f1), fnb) + cvz(rot_fwd<MDH>(R1, n1), nb));
+                    if (MDH) accq[j + 1] = accq[j + 1] + (vjp_zcross(f1, fb1) + vjp_zcross(n1, nb1));
+                    else accq[j + 1] = accq[j + 1] + (vjp_zcross(rot_fwd<MDH>(R1, f1), fnb) + vjp_zcross(rot_fwd<MDH>(R1, n1), nb));
                     Fq[j] = Fb; Nq[j] = nb;
                     fb = fb1; nb = nb1;
                 } else {
@@ -172,15 +165,15 @@ RTB_HD void coriolis_vjp_lane(LinksP links, int n_rt, InQ qin, InQd qdin, Begin 
                     // the link terms:  F = m (a + wd x r + wu x (ww x r) + ww x (wu x r)),  N = I wd + wu x (I ww) + ww x (I wu)
                     const V3 acb = l.m * Fb;
                     ab = ab + acb;
-                    wdb = cross_add(rc, acb, wdb + cv_inertia_t_times(l, Nb));
+                    wdb = cross_add(rc, acb, wdb + vjp_inertia_t_times(l, Nb));
                     wub = cross_add(cross(ww, rc), acb, wub);
                     wub = cross_add(rc, cross(acb, ww), wub);
                     wub = cross_add(inertia_times(l, ww), Nb, wub);
-                    wub = wub + cv_inertia_t_times(l, cross(Nb, ww));
+                    wub = wub + vjp_inertia_t_times(l, cross(Nb, ww));
                     wwb = cross_add(cross(wu, rc), acb, wwb);
                     wwb = cross_add(rc, cross(acb, wu), wwb);
                     wwb = cross_add(inertia_times(l, wu), Nb, wwb);
-                    wwb = wwb + cv_inertia_t_times(l, cross(Nb, wu));
+                    wwb = wwb + vjp_inertia_t_times(l, cross(Nb, wu));
                 }
                 // the recursion step.  The state of link j - 1 is not taped: the forward step is run backwards from the state of link j (a rotation
                 // and a few products; the base is at rest exactly)
@@ -195,16 +188,16 @@ RTB_HD void coriolis_vjp_lane(LinksP links, int n_rt, InQ qin, InQd qdin, Begin 
                     wdp = j > 0 ? rot_fwd<MDH>(R, twd) : o;
                     ap = j > 0 ? cv_sub(rot_fwd<MDH>(R, a), cross_add(wdp, ps, cross_add(wup, cross(wwp, ps), cross(wwp, cross(wup, ps))))) : o;
                     const V3 Xb = rot_fwd<MDH>(R, ab);
-                    t = -cvz(a, ab);
+                    t = -vjp_zcross(a, ab);
                     abp = Xb;
                     wdbp = cross(ps, Xb);
                     wubp = cross_add(ps, cross(Xb, wwp), cross(cross(wwp, ps), Xb));
                     wwbp = cross_add(ps, cross(Xb, wup), cross(cross(wup, ps), Xb));
-                    t = t - cvz(twd, wdb);
+                    t = t - vjp_zcross(twd, wdb);
                     wdbp = wdbp + rot_fwd<MDH>(R, wdb);
-                    const V3 tub = wub + cv_zrate_cross(qdw, wdb), twb = wwb + cv_zrate_cross(qdu, wdb);
-                    oqd = wub.z + cvz(wdb, tw);
-                    t = t - (cvz(tu, tub) + cvz(tw, twb));
+                    const V3 tub = wub + vjp_zrate_cross(qdw, wdb), twb = wwb + vjp_zrate_cross(qdu, wdb);
+                    oqd = wub.z + vjp_zcross(wdb, tw);
+                    t = t - (vjp_zcross(tu, tub) + vjp_zcross(tw, twb));
                     wubp = wubp + rot_fwd<MDH>(R, tub);
                     wwbp = wwbp + rot_fwd<MDH>(R, twb);
                 } else {
@@ -220,11 +213,11 @@ RTB_HD void coriolis_vjp_lane(LinksP links, int n_rt, InQ qin, InQd qdin, Begin 
                     ap = j > 0 ? rot_fwd<MDH>(R, cv_sub(a, cross_add(wd, ps, cross_add(wu, cross(ww, ps), cross(ww, cross(wu, ps)))))) : o;
                     abp = rot_fwd<MDH>(R, ab);
                     const V3 t3b = rot_fwd<MDH>(R, wdb), tub = rot_fwd<MDH>(R, wub), twb = rot_fwd<MDH>(R, wwb);
-                    t = -(cvz(ap, abp) + (cvz(t3, t3b) + (cvz(tu, tub) + cvz(tw, twb))));
+                    t = -(vjp_zcross(ap, abp) + (vjp_zcross(t3, t3b) + (vjp_zcross(tu, tub) + vjp_zcross(tw, twb))));
                     wdbp = t3b;
-                    wubp = tub + cv_zrate_cross(qdw, t3b);
-                    wwbp = twb + cv_zrate_cross(qdu, t3b);
-                    oqd = tub.z + cvz(t3b, wwp);
+                    wubp = tub + vjp_zrate_cross(qdw, t3b);
+                    wwbp = twb + vjp_zrate_cross(qdu, t3b);
+                    oqd = tub.z + vjp_zcross(t3b, wwp);
                 }
                 accq[j] = accq[j] + t;
                 accd[j] = accd[j] + oqd;
@@ -241,7 +234,6 @@ RTB_HD void coriolis_vjp_lane(LinksP links, int n_rt, InQ qin, InQd qdin, Begin 
 #ifndef RTB_CORIOLIS_VJP_LANE_ONLY      // (a host-side replay of the lane body includes this file for coriolis_vjp_lane alone)
 
 typedef const __attribute__((address_space(4))) DevLink *CvLinks;
-constexpr int kCvW = 64;
 constexpr int kCoriolisVjpMaxJoints = 16;      // the forward kernel's built-in sizes
 constexpr int kCoriolisVjpRegMax = 7;          // the largest compile-time joint count: eight links spill (DESIGN 4.16 has the register table)
 
@@ -254,41 +246,42 @@ struct CoriolisVjpParams {
 // for the run-time-n form
 inline __host__ __device__ int coriolis_vjp_stride(int n, bool rt) { return (2 * n + (rt ? n : n * n)) | 1; }
 
-// One tile of 64 samples.  gq / gqd NULL: not stored.
+// One tile of 64 samples.  gq / gqd NULL: not stored.  This unit keeps its own staging and flush, and its lane body its own sweep 2: with
+// vjp_tile.h's phases (or vjp_dh_sweep2) in their place the Panda's adjoint measured 0.5 to 4 % slower (profiles/vjp_tile_refactor_ab.json).
 template <int NJ, bool MDH>
 __device__ __forceinline__ void coriolis_vjp_tile(const CoriolisVjpParams &cp, CvLinks links, int n, int stride, int64_t tile, const double *__restrict__ q,
                                                   const double *__restrict__ qd, const double *__restrict__ gC, double *__restrict__ gq,
                                                   double *__restrict__ gqd, double *lds, int lane)
 {
-    const int64_t cfg0 = tile * kCvW;
+    const int64_t cfg0 = tile * kWave;
     const int64_t left = cp.N - cfg0;
-    const int ncfg = left < kCvW ? (int)left : kCvW;
+    const int ncfg = left < kWave ? (int)left : kWave;
     const int nn = n * n;
     const int count = ncfg * n, mcount = ncfg * nn;
     const double *qg = q + cfg0 * n, *dg = qd + cfg0 * n, *mg = gC + cfg0 * nn;
     if constexpr (NJ > 0) {
         // the 2 NJ + NJ^2 coalesced loads of the tile, UNCONDITIONAL (an element past the ragged tail reads element 0 of the tile; the zeros are
-        // selected afterwards: k_rne_vjp tells why), all in flight before the first LDS write
+        // selected afterwards: vjp_tile.h tells why), all in flight before the first LDS write
         double rq[NJ], rd[NJ], rm[NJ * NJ];
 #pragma unroll
-        for (int k = 0; k < NJ; ++k) { const int f = lane + kCvW * k, fc = f < count ? f : 0; rq[k] = qg[fc]; rd[k] = dg[fc]; }
+        for (int k = 0; k < NJ; ++k) { const int f = lane + kWave * k, fc = f < count ? f : 0; rq[k] = qg[fc]; rd[k] = dg[fc]; }
 #pragma unroll
-        for (int k = 0; k < NJ * NJ; ++k) { const int f = lane + kCvW * k; rm[k] = mg[f < mcount ? f : 0]; }
+        for (int k = 0; k < NJ * NJ; ++k) { const int f = lane + kWave * k; rm[k] = mg[f < mcount ? f : 0]; }
         sched_fence();
 #pragma unroll
         for (int k = 0; k < NJ; ++k) {
-            const int f = lane + kCvW * k;
+            const int f = lane + kWave * k;
             double *dst = lds + (f / NJ) * stride + (f % NJ);
             dst[0] = f < count ? rq[k] : 0.0;
             dst[NJ] = f < count ? rd[k] : 0.0;
         }
 #pragma unroll
         for (int k = 0; k < NJ * NJ; ++k) {
-            const int f = lane + kCvW * k;
+            const int f = lane + kWave * k;
             lds[(f / (NJ * NJ)) * stride + 2 * NJ + (f % (NJ * NJ))] = f < mcount ? rm[k] : 0.0;
         }
     } else {
-        for (int f = lane; f < kCvW * n; f += kCvW) {
+        for (int f = lane; f < kWave * n; f += kWave) {
             double *dst = lds + (f / n) * stride + (f % n);
             dst[0] = f < count ? qg[f] : 0.0;
             dst[n] = f < count ? dg[f] : 0.0;
@@ -316,7 +309,7 @@ __device__ __forceinline__ void coriolis_vjp_tile(const CoriolisVjpParams &cp, C
         double r[2][NJ];
 #pragma unroll
         for (int k = 0; k < NJ; ++k) {
-            const int f = lane + kCvW * k;
+            const int f = lane + kWave * k;
             const double *src = lds + (f / NJ) * stride + (f % NJ);
             r[0][k] = src[0]; r[1][k] = src[NJ];
         }
@@ -325,12 +318,12 @@ __device__ __forceinline__ void coriolis_vjp_tile(const CoriolisVjpParams &cp, C
             if (!gout[a]) continue;          // wave-uniform
 #pragma unroll
             for (int k = 0; k < NJ; ++k) {
-                const int f = lane + kCvW * k;
+                const int f = lane + kWave * k;
                 if (f < count) __builtin_nontemporal_store(r[a][k], gout[a] + f);
             }
         }
     } else {
-        for (int f = lane; f < count; f += kCvW) {
+        for (int f = lane; f < count; f += kWave) {
             const double *src = lds + (f / n) * stride + (f % n);
             if (gout[0]) gout[0][f] = src[0];
             if (gout[1]) gout[1][f] = src[n];
@@ -340,7 +333,7 @@ __device__ __forceinline__ void coriolis_vjp_tile(const CoriolisVjpParams &cp, C
 
 // compile-time joint count: one tile per single-wave workgroup, one wave per SIMD
 template <int NJ, bool MDH>
-__global__ __launch_bounds__(kCvW, 1) void k_coriolis_vjp(CoriolisVjpParams cp, const DevLink *links_g, const double *__restrict__ q,
+__global__ __launch_bounds__(kWave, 1) void k_coriolis_vjp(CoriolisVjpParams cp, const DevLink *links_g, const double *__restrict__ q,
                                                            const double *__restrict__ qd, const double *__restrict__ gC, double *__restrict__ gq,
                                                            double *__restrict__ gqd)
 {
@@ -351,14 +344,14 @@ __global__ __launch_bounds__(kCvW, 1) void k_coriolis_vjp(CoriolisVjpParams cp, 
 // run-time joint count (8 .. 16 joints, or more tiles than a grid has blocks): grid-stride over tiles, the tape
 // in private memory
 template <bool MDH>
-__global__ __launch_bounds__(kCvW) void k_coriolis_vjp_rt(CoriolisVjpParams cp, const DevLink *links_g, const double *__restrict__ q,
+__global__ __launch_bounds__(kWave) void k_coriolis_vjp_rt(CoriolisVjpParams cp, const DevLink *links_g, const double *__restrict__ q,
                                                           const double *__restrict__ qd, const double *__restrict__ gC, double *__restrict__ gq,
                                                           double *__restrict__ gqd)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int n = cp.n;
     const int stride = coriolis_vjp_stride(n, true);
-    const int64_t tiles = (cp.N + kCvW - 1) / kCvW;
+    const int64_t tiles = (cp.N + kWave - 1) / kWave;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         coriolis_vjp_tile<0, MDH>(cp, (CvLinks)links_g, n, stride, tile, q, qd, gC, gq, gqd, lds, threadIdx.x);
         __syncthreads();
@@ -368,20 +361,12 @@ __global__ __launch_bounds__(kCvW) void k_coriolis_vjp_rt(CoriolisVjpParams cp, 
 #if RTB_HOST_SIDE
 namespace {
 
-template <class K>
-void coriolis_vjp_go(K k, dim3 grid, size_t lds, hipStream_t s, const CoriolisVjpParams &cp, const DevLink *links, const double *q, const double *qd,
-                     const double *gC, double *gq, double *gqd)
-{
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, grid, dim3(kCvW), lds, s, cp, links, q, qd, gC, gq, gqd);
-}
-
 template <int NJ>
 void coriolis_vjp_go_nj(bool mdh, dim3 grid, size_t lds, hipStream_t s, const CoriolisVjpParams &cp, const DevLink *links, const double *q,
                         const double *qd, const double *gC, double *gq, double *gqd)
 {
-    if (mdh) coriolis_vjp_go(k_coriolis_vjp<NJ, true>, grid, lds, s, cp, links, q, qd, gC, gq, gqd);
-    else coriolis_vjp_go(k_coriolis_vjp<NJ, false>, grid, lds, s, cp, links, q, qd, gC, gq, gqd);
+    if (mdh) vjp_go(k_coriolis_vjp<NJ, true>, grid, lds, s, cp, links, q, qd, gC, gq, gqd);
+    else vjp_go(k_coriolis_vjp<NJ, false>, grid, lds, s, cp, links, q, qd, gC, gq, gqd);
 }
 
 }  // namespace
@@ -394,10 +379,10 @@ int launch_coriolis_vjp(const Dyn *d, const DevLink *links, const double *q, con
     if (d->n < 1 || d->n > kCoriolisVjpMaxJoints) { set_error("coriolis_vjp: chains of 1..16 joints"); return RTBHIP_ELIMIT; }
     CoriolisVjpParams cp;
     cp.n = d->n; cp.pad_ = 0; cp.N = N;
-    const int64_t tiles = (N + kCvW - 1) / kCvW;
+    const int64_t tiles = (N + kWave - 1) / kWave;
     const bool mdh = d->mdh != 0;
     const bool rt = d->n > kCoriolisVjpRegMax || tiles > 0x7fffffff;
-    const size_t lds = (size_t)kCvW * coriolis_vjp_stride(d->n, rt) * sizeof(double);
+    const size_t lds = (size_t)kWave * coriolis_vjp_stride(d->n, rt) * sizeof(double);
     dim3 grid((unsigned)(rt && tiles > 65536 ? 65536 : tiles));      // the run-time-n kernel strides over the tiles
     switch (rt ? 0 : d->n) {
     case 1: coriolis_vjp_go_nj<1>(mdh, grid, lds, s, cp, links, q, qd, gC, gq, gqd); break;
@@ -408,11 +393,11 @@ int launch_coriolis_vjp(const Dyn *d, const DevLink *links, const double *q, con
     case 6: coriolis_vjp_go_nj<6>(mdh, grid, lds, s, cp, links, q, qd, gC, gq, gqd); break;
     case 7: coriolis_vjp_go_nj<7>(mdh, grid, lds, s, cp, links, q, qd, gC, gq, gqd); break;
     default:
-        if (mdh) coriolis_vjp_go(k_coriolis_vjp_rt<true>, grid, lds, s, cp, links, q, qd, gC, gq, gqd);
-        else coriolis_vjp_go(k_coriolis_vjp_rt<false>, grid, lds, s, cp, links, q, qd, gC, gq, gqd);
+        if (mdh) vjp_go(k_coriolis_vjp_rt<true>, grid, lds, s, cp, links, q, qd, gC, gq, gqd);
+        else vjp_go(k_coriolis_vjp_rt<false>, grid, lds, s, cp, links, q, qd, gC, gq, gqd);
         break;
     }
-    note_launch((int)grid.x, kCvW, (int)lds);
+    note_launch((int)grid.x, kWave, (int)lds);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "k_coriolis_vjp launch");
     return RTBHIP_OK;

@@ -25,21 +25,12 @@
 // Tape: 15 doubles per link (w, wd, a; f, n) -- 210 VGPRs for seven links, 240 for eight, plus the working set: one wave per SIMD
 // (__launch_bounds__(64, 1), the 512-entry register file).  I/O as k_rne: the wave's (64 x n) blocks of q, qd, qdd and gtau are contiguous in
 // memory, loaded coalesced into a lane-major LDS tile (odd row stride); gq, gqd, gqdd overwrite the q, qd, qdd slots and leave the same way.
-#include "rne_device.h"
+#include "vjp_tile.h"
 
 namespace rtbhip {
 
 // every floating-point operation as written (see rne_device.h): the float32 instantiation must return the fp64 one's numbers, rounded once
 #pragma clang fp contract(off)
-
-RTB_HD double zcross(V3 a, V3 b) { return __builtin_fma(a.x, b.y, -(a.y * b.x)); }       // (a x b).z
-RTB_HD V3 zrate_cross(double s, V3 v) { return v3(-(s * v.y), s * v.x, 0.0); }            // (0, 0, s) x v
-template <class LinkT>
-RTB_HD V3 inertia_t_times(const LinkT &l, V3 v)      // the transpose of inertia_times
-{
-    return v3(__builtin_fma(l.I[2], v.z, __builtin_fma(l.I[1], v.y, l.I[0] * v.x)), __builtin_fma(l.I[5], v.z, __builtin_fma(l.I[4], v.y, l.I[3] * v.x)),
-              __builtin_fma(l.I[8], v.z, __builtin_fma(l.I[7], v.y, l.I[6] * v.x)));
-}
 
 // One sample.  links: the wave-uniform link table, every link revolute.  qin / qdin / qddin / gin: per-lane readers  in(j) -> double;
 // gq / gqd / gqdd: writers  out(j, v).  q is read up front; qd_j, qdd_j and gtau_j must stay readable until gq_j, gqd_j, gqdd_j have been written
@@ -87,23 +78,7 @@ RTB_HD void rne_vjp_lane(LinksP links, int n_rt, V3 grav, V3 ftip, V3 ntip, InQ 
     }
 
     // ---- 2. primal backward recursion: (F_j, N_j) -> (f_j, n_j) in place
-    {
-        V3 f = ftip, nn = ntip, psn = v3(0, 0, 0);
-        Rot Rn = {0, 1, 0, 1, 0};
-#pragma unroll
-        for (int jj = 0; jj < n; ++jj) {
-            const int j = n - 1 - jj;
-            const auto &l = links[j];
-            const V3 ps = link_offset<MDH>(l, l.d), rc = v3(l.rx, l.ry, l.rz);
-            const V3 fn = jj == 0 ? f : rot_fwd<MDH>(Rn, f), gn = jj == 0 ? nn : rot_fwd<MDH>(Rn, nn);
-            const V3 F = Fq[j];
-            const V3 nj = MDH ? cross_add(psn, fn, cross_add(rc, F, gn + Nq[j])) : cross_add(ps, fn, cross_add(ps + rc, F, gn + Nq[j]));
-            f = fn + F; nn = nj;
-            Fq[j] = f; Nq[j] = nn;
-            Rn = Rot{st[j], ct[j], l.sa, l.ca, 0}; psn = ps;
-            if (NJ > 0) sched_fence();
-        }
-    }
+    vjp_dh_sweep2<NJ, MDH>(links, n, st, ct, Fq, Nq, ftip, ntip, 0);
 
     // ---- 3. adjoint of the backward recursion, base -> tip: (f_j, n_j) -> the adjoints of (F_j, N_j) in place
     {
@@ -125,8 +100,8 @@ RTB_HD void rne_vjp_lane(LinksP links, int n_rt, V3 grav, V3 ftip, V3 ntip, InQ 
                 if (MDH) fnb = cross_add(nb, link_offset<MDH>(l1, l1.d), fnb);
                 const V3 f1 = Fq[j + 1], n1 = Nq[j + 1];
                 const V3 fb1 = rot_inv<MDH>(R1, fnb), nb1 = rot_inv<MDH>(R1, nb);
-                if (MDH) th[j + 1] = zcross(f1, fb1) + zcross(n1, nb1);
-                else th[j + 1] = zcross(rot_fwd<MDH>(R1, f1), fnb) + zcross(rot_fwd<MDH>(R1, n1), nb);
+                if (MDH) th[j + 1] = vjp_zcross(f1, fb1) + vjp_zcross(n1, nb1);
+                else th[j + 1] = vjp_zcross(rot_fwd<MDH>(R1, f1), fnb) + vjp_zcross(rot_fwd<MDH>(R1, n1), nb);
                 Fq[j] = Fb; Nq[j] = nb;
                 fb = fb1; nb = nb1;
             } else {
@@ -150,28 +125,28 @@ RTB_HD void rne_vjp_lane(LinksP links, int n_rt, V3 grav, V3 ftip, V3 ntip, InQ 
             // the link terms:  F = m (a + wd x r + w x (w x r)),  N = I wd + w x (I w)
             const V3 acb = l.m * Fb;
             ab = ab + acb;
-            wdb = cross_add(rc, acb, wdb + inertia_t_times(l, Nb));
+            wdb = cross_add(rc, acb, wdb + vjp_inertia_t_times(l, Nb));
             wb = cross_add(cross(w, rc), acb, wb);
             wb = cross_add(rc, cross(acb, w), wb);
             wb = cross_add(inertia_times(l, w), Nb, wb);
-            wb = wb + inertia_t_times(l, cross(Nb, w));
+            wb = wb + vjp_inertia_t_times(l, cross(Nb, w));
             // the recursion step
             const V3 wp = j > 0 ? W[j > 0 ? j - 1 : 0] : v3(0, 0, 0), wdp = j > 0 ? WD[j > 0 ? j - 1 : 0] : v3(0, 0, 0), ap = j > 0 ? A[j > 0 ? j - 1 : 0] : grav;
             V3 wbp, wdbp, abp;
             double t, oqd, oqdd;
             if (MDH) {
                 const V3 Xb = rot_fwd<MDH>(R, ab);
-                t = -zcross(a, ab);
+                t = -vjp_zcross(a, ab);
                 abp = Xb;
                 wdbp = cross(ps, Xb);
                 wbp = cross_add(ps, cross(Xb, wp), cross(cross(wp, ps), Xb));
-                t = t - zcross(rot_inv<MDH>(R, wdp), wdb);
+                t = t - vjp_zcross(rot_inv<MDH>(R, wdp), wdb);
                 wdbp = wdbp + rot_fwd<MDH>(R, wdb);
                 const V3 t1 = rot_inv<MDH>(R, wp);
-                const V3 t1b = wb + zrate_cross(qdj, wdb);
-                oqd = wb.z + zcross(wdb, t1);
+                const V3 t1b = wb + vjp_zrate_cross(qdj, wdb);
+                oqd = wb.z + vjp_zcross(wdb, t1);
                 oqdd = wdb.z;
-                t = t - zcross(t1, t1b);
+                t = t - vjp_zcross(t1, t1b);
                 wbp = wbp + rot_fwd<MDH>(R, t1b);
             } else {
                 wdb = cross_add(ps, ab, wdb);
@@ -180,11 +155,11 @@ RTB_HD void rne_vjp_lane(LinksP links, int n_rt, V3 grav, V3 ftip, V3 ntip, InQ 
                 abp = rot_fwd<MDH>(R, ab);
                 const V3 t3b = rot_fwd<MDH>(R, wdb), t1b = rot_fwd<MDH>(R, wb);
                 const V3 t1 = addz(wp, qdj), t3 = addz(wdp + crossz(wp, qdj), qddj);
-                t = -(zcross(ap, abp) + (zcross(t3, t3b) + zcross(t1, t1b)));
+                t = -(vjp_zcross(ap, abp) + (vjp_zcross(t3, t3b) + vjp_zcross(t1, t1b)));
                 wdbp = t3b;
                 oqdd = t3b.z;
-                wbp = t1b + zrate_cross(qdj, t3b);
-                oqd = t1b.z + zcross(t3b, wp);
+                wbp = t1b + vjp_zrate_cross(qdj, t3b);
+                oqd = t1b.z + vjp_zcross(t3b, wp);
             }
             gq(j, th[j] + t);
             gqd(j, __builtin_fma(l.gb, g, oqd));
@@ -198,7 +173,6 @@ RTB_HD void rne_vjp_lane(LinksP links, int n_rt, V3 grav, V3 ftip, V3 ntip, InQ 
 #ifndef RTB_RNE_VJP_LANE_ONLY      // (a host-side replay of the lane body includes this file for rne_vjp_lane alone)
 
 typedef const __attribute__((address_space(4))) DevLink *VjpLinks;
-constexpr int kVjpW = 64;
 
 struct RneVjpParams {
     int32_t n, has_fext;
@@ -208,57 +182,25 @@ struct RneVjpParams {
 };
 
 // LDS row of one sample: q | qd | qdd | gtau, 4 n doubles; an odd stride (conflict-free rows) while the tile stays within 64 KiB
-inline __host__ __device__ int rne_vjp_stride(int n) { return (4 * n + 1) * kVjpW * 8 <= 65536 ? 4 * n + 1 : 4 * n; }
+inline __host__ __device__ int rne_vjp_stride(int n) { return (4 * n + 1) * kWave * 8 <= 65536 ? 4 * n + 1 : 4 * n; }
 
 // One tile of 64 samples.  S: the storage type of q, qd, qdd, gtau and of the gradients -- double, or float (widened after the load, rounded
 // once before the store).  qd / qdd NULL: zeros.  gq / gqd / gqdd NULL: not stored (the lane body forms all three gradients either way: they share
-// the four sweeps, and what is particular to one of them is a handful of operations per link).
+// the four sweeps, and what is particular to one of them is a handful of operations per link).  The staging and the flush are vjp_tile.h's phases.
 template <int NJ, bool MDH, class S>
 __device__ __forceinline__ void rne_vjp_tile(const RneVjpParams &rp, VjpLinks links, int n, int stride, int64_t tile, const S *__restrict__ q,
                                              const S *__restrict__ qd, const S *__restrict__ qdd, const S *__restrict__ gtau, S *__restrict__ gq,
                                              S *__restrict__ gqd, S *__restrict__ gqdd, double *lds, int lane)
 {
-    const int64_t cfg0 = tile * kVjpW;
-    const int64_t left = rp.N - cfg0;
-    const int ncfg = left < kVjpW ? (int)left : kVjpW;
-    const int count = ncfg * n;
-    const S *gin[4] = {q + cfg0 * n, qd ? qd + cfg0 * n : nullptr, qdd ? qdd + cfg0 * n : nullptr, gtau + cfg0 * n};
-    if constexpr (NJ > 0) {
-        // the 4 * NJ coalesced loads of the tile, then the LDS transposition.  The loads are UNCONDITIONAL -- an element past the ragged tail
-        // reads element 0 of the tile (a tile has at least one row), an absent qd / qdd reads q -- and the zeros are selected afterwards, the
-        // values still in their storage type: a load inside the bounds branch takes its float -> double conversion, and with it a wait for
-        // that one load, into the branch: one dependent HBM round trip per element.  As built the loads overlap: each wait lets the
-        // oldest load complete while a dozen or more stay in flight, and the counter never drains before the last one has been issued
-        S r[4][NJ];
-#pragma unroll
-        for (int k = 0; k < NJ; ++k) {
-            const int f = lane + kVjpW * k, fc = f < count ? f : 0;
-#pragma unroll
-            for (int a = 0; a < 4; ++a) r[a][k] = (gin[a] ? gin[a] : gin[0])[fc];
-        }
-        sched_fence();
-#pragma unroll
-        for (int k = 0; k < NJ; ++k) {
-            const int f = lane + kVjpW * k;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-                if (!gin[a] || f >= count) r[a][k] = S(0);
-        }
-#pragma unroll
-        for (int k = 0; k < NJ; ++k) {
-            const int f = lane + kVjpW * k;
-            double *dst = lds + (f / NJ) * stride + (f % NJ);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) dst[a * NJ] = (double)r[a][k];
-        }
-    } else {
-        for (int f = lane; f < kVjpW * n; f += kVjpW) {
-            double *dst = lds + (f / n) * stride + (f % n);
-            for (int a = 0; a < 4; ++a) dst[a * n] = (gin[a] && f < count) ? (double)gin[a][f] : 0.0;
-        }
-    }
+    const VjpTile t = vjp_tile_of(tile, rp.N, n);
+    const int64_t at = t.cfg0 * n;
+    const S *const gin[4] = {q + at, qd ? qd + at : nullptr, qdd ? qdd + at : nullptr, gtau + at};
+    VjpCols<NJ, 4, S> cols;
+    vjp_load_cols<NJ, true>(gin, t, lane, cols);
+    sched_fence();
+    vjp_stage_cols<NJ, true>(gin, t, n, stride, lane, cols, lds);
     __syncthreads();
-    if (lane < ncfg) {
+    if (lane < t.ncfg) {
         double *mine = lds + lane * stride;
         const V3 grav = v3(rp.grav[0], rp.grav[1], rp.grav[2]);
         const V3 ftip = rp.has_fext ? v3(rp.fext[0], rp.fext[1], rp.fext[2]) : v3(0, 0, 0);
@@ -268,37 +210,13 @@ __device__ __forceinline__ void rne_vjp_tile(const RneVjpParams &rp, VjpLinks li
                               [&](int j, double v) { mine[n + j] = v; }, [&](int j, double v) { mine[2 * n + j] = v; });
     }
     __syncthreads();
-    S *gout[3] = {gq ? gq + cfg0 * n : nullptr, gqd ? gqd + cfg0 * n : nullptr, gqdd ? gqdd + cfg0 * n : nullptr};
-    if constexpr (NJ > 0) {
-        double r[3][NJ];
-#pragma unroll
-        for (int k = 0; k < NJ; ++k) {
-            const int f = lane + kVjpW * k;
-            const double *src = lds + (f / NJ) * stride + (f % NJ);
-#pragma unroll
-            for (int a = 0; a < 3; ++a) r[a][k] = src[a * NJ];
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (!gout[a]) continue;          // wave-uniform
-#pragma unroll
-            for (int k = 0; k < NJ; ++k) {
-                const int f = lane + kVjpW * k;
-                if (f < count) __builtin_nontemporal_store((S)r[a][k], gout[a] + f);
-            }
-        }
-    } else {
-        for (int f = lane; f < count; f += kVjpW) {
-            const double *src = lds + (f / n) * stride + (f % n);
-            for (int a = 0; a < 3; ++a)
-                if (gout[a]) gout[a][f] = (S)src[a * n];
-        }
-    }
+    S *const gout[3] = {gq ? gq + at : nullptr, gqd ? gqd + at : nullptr, gqdd ? gqdd + at : nullptr};
+    vjp_tile_flush<NJ, true>(gout, t, n, stride, lane, lds);
 }
 
 // compile-time joint count: one tile per single-wave workgroup (as k_rne: no grid-stride loop), one wave per SIMD
 template <int NJ, bool MDH, class S>
-__global__ __launch_bounds__(kVjpW, 1) void k_rne_vjp(RneVjpParams rp, const DevLink *links_g, const S *__restrict__ q, const S *__restrict__ qd,
+__global__ __launch_bounds__(kWave, 1) void k_rne_vjp(RneVjpParams rp, const DevLink *links_g, const S *__restrict__ q, const S *__restrict__ qd,
                                                        const S *__restrict__ qdd, const S *__restrict__ gtau, S *__restrict__ gq, S *__restrict__ gqd,
                                                        S *__restrict__ gqdd)
 {
@@ -308,14 +226,14 @@ __global__ __launch_bounds__(kVjpW, 1) void k_rne_vjp(RneVjpParams rp, const Dev
 
 // run-time joint count (9 .. 32 joints, or more tiles than a grid has blocks): grid-stride over tiles, the tape in private memory
 template <bool MDH, class S>
-__global__ __launch_bounds__(kVjpW) void k_rne_vjp_rt(RneVjpParams rp, const DevLink *links_g, const S *__restrict__ q, const S *__restrict__ qd,
+__global__ __launch_bounds__(kWave) void k_rne_vjp_rt(RneVjpParams rp, const DevLink *links_g, const S *__restrict__ q, const S *__restrict__ qd,
                                                       const S *__restrict__ qdd, const S *__restrict__ gtau, S *__restrict__ gq, S *__restrict__ gqd,
                                                       S *__restrict__ gqdd)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int n = rp.n;
     const int stride = rne_vjp_stride(n);
-    const int64_t tiles = (rp.N + kVjpW - 1) / kVjpW;
+    const int64_t tiles = (rp.N + kWave - 1) / kWave;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         rne_vjp_tile<0, MDH, S>(rp, (VjpLinks)links_g, n, stride, tile, q, qd, qdd, gtau, gq, gqd, gqdd, lds, threadIdx.x);
         __syncthreads();
@@ -329,8 +247,8 @@ template <int NJ, class S>
 void vjp_launch_nj(bool mdh, dim3 grid, size_t lds, hipStream_t s, const RneVjpParams &rp, const DevLink *links, const S *q, const S *qd, const S *qdd,
                    const S *gtau, S *gq, S *gqd, S *gqdd)
 {
-    if (mdh) hipLaunchKernelGGL((k_rne_vjp<NJ, true, S>), grid, dim3(kVjpW), lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd);
-    else hipLaunchKernelGGL((k_rne_vjp<NJ, false, S>), grid, dim3(kVjpW), lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd);
+    if (mdh) hipLaunchKernelGGL((k_rne_vjp<NJ, true, S>), grid, dim3(kWave), lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd);
+    else hipLaunchKernelGGL((k_rne_vjp<NJ, false, S>), grid, dim3(kWave), lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd);
 }
 
 template <class S>
@@ -345,8 +263,8 @@ int vjp_launch(const Dyn *d, const DevLink *links, const S *q, const S *qd, cons
     rp.N = N;
     for (int i = 0; i < 3; i++) rp.grav[i] = grav3[i];
     for (int i = 0; i < 6; i++) rp.fext[i] = fext6 ? fext6[i] : 0.0;
-    const size_t lds = (size_t)kVjpW * rne_vjp_stride(d->n) * sizeof(double);
-    const int64_t tiles = (N + kVjpW - 1) / kVjpW;
+    const size_t lds = (size_t)kWave * rne_vjp_stride(d->n) * sizeof(double);
+    const int64_t tiles = (N + kWave - 1) / kWave;
     const bool mdh = d->mdh != 0;
     const bool rt = d->n > 8 || tiles > 0x7fffffff;
     int64_t g = tiles;
@@ -362,11 +280,11 @@ int vjp_launch(const Dyn *d, const DevLink *links, const S *q, const S *qd, cons
     case 7: vjp_launch_nj<7, S>(mdh, grid, lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd); break;
     case 8: vjp_launch_nj<8, S>(mdh, grid, lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd); break;
     default:
-        if (mdh) hipLaunchKernelGGL((k_rne_vjp_rt<true, S>), grid, dim3(kVjpW), lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd);
-        else hipLaunchKernelGGL((k_rne_vjp_rt<false, S>), grid, dim3(kVjpW), lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd);
+        if (mdh) hipLaunchKernelGGL((k_rne_vjp_rt<true, S>), grid, dim3(kWave), lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd);
+        else hipLaunchKernelGGL((k_rne_vjp_rt<false, S>), grid, dim3(kWave), lds, s, rp, links, q, qd, qdd, gtau, gq, gqd, gqdd);
         break;
     }
-    note_launch((int)grid.x, kVjpW, (int)lds);
+    note_launch((int)grid.x, kWave, (int)lds);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "k_rne_vjp launch");
     return RTBHIP_OK;

@@ -33,6 +33,7 @@
 // gC, staged per pass), then the branch slots and the kept states, [double][lane]; gq and gqd overwrite the q and qd slots and leave as contiguous non-temporal
 // stores.
 #include "tree_kernels.h"
+#include "vjp_tile.h"
 
 namespace rtbhip {
 
@@ -41,12 +42,8 @@ namespace rtbhip {
 constexpr int kTreeCoriolisVjpMaxGroups = 20;      // the forward kernel's built-in sizes (tree_dyn_kernels.hip: kTreeDynMax)
 constexpr int kTcSD = kTreeBilinearSlotDoubles;
 
-RTB_HD double tcz(V3 a, V3 b) { return __builtin_fma(a.x, b.y, -(a.y * b.x)); }       // (a x b).z = ((0, 0, 1) x a) . b
 RTB_HD V3 tc_zero() { return v3(0, 0, 0); }
 RTB_HD V3 tc_zx(double s, V3 v, V3 acc) { return v3(__builtin_fma(-s, v.y, acc.x), __builtin_fma(s, v.x, acc.y), acc.z); }      // acc + (0, 0, s) x v
-template <class Slot> RTB_HD V3 tc_get(Slot &slot, int b) { return v3(slot(b + 0), slot(b + 1), slot(b + 2)); }
-template <class Slot> RTB_HD void tc_put(Slot &slot, int b, V3 v) { slot(b + 0) = v.x; slot(b + 1) = v.y; slot(b + 2) = v.z; }
-template <class Slot> RTB_HD void tc_add(Slot &slot, int b, V3 v) { slot(b + 0) += v.x; slot(b + 1) += v.y; slot(b + 2) += v.z; }
 // I [l; a] = [M l + a x h; I_bar a + h x l]  (symmetric: it is its own transpose)
 template <class G> RTB_HD void tc_inertia(const G &g, V3 l, V3 a, V3 &ol, V3 &oa)
 {
@@ -117,8 +114,8 @@ RTB_HD void tree_coriolis_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin
                     pul = tc_zero(); pua = tc_zero(); pwl = tc_zero(); pwa = tc_zero(); pal = tc_zero(); paa = tc_zero();
                 } else if (g.parent_slot >= 0) {
                     const int b = g.parent_slot * kTcSD;
-                    pul = tc_get(slot, b); pua = tc_get(slot, b + 3); pwl = tc_get(slot, b + 6); pwa = tc_get(slot, b + 9);
-                    pal = tc_get(slot, b + 12); paa = tc_get(slot, b + 15);
+                    pul = vjp_slot_get(slot, b); pua = vjp_slot_get(slot, b + 3); pwl = vjp_slot_get(slot, b + 6); pwa = vjp_slot_get(slot, b + 9);
+                    pal = vjp_slot_get(slot, b + 12); paa = vjp_slot_get(slot, b + 15);
                 } else {
                     pul = ul; pua = ua; pwl = wl; pwa = wa; pal = al; paa = aa;
                 }
@@ -140,13 +137,13 @@ RTB_HD void tree_coriolis_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin
                 }
                 if (g.save_slot >= 0) {
                     const int b = g.save_slot * kTcSD;
-                    tc_put(slot, b, ul); tc_put(slot, b + 3, ua); tc_put(slot, b + 6, wl); tc_put(slot, b + 9, wa);
-                    tc_put(slot, b + 12, al); tc_put(slot, b + 15, aa);
+                    vjp_slot_put(slot, b, ul); vjp_slot_put(slot, b + 3, ua); vjp_slot_put(slot, b + 6, wl); vjp_slot_put(slot, b + 9, wa);
+                    vjp_slot_put(slot, b + 12, al); vjp_slot_put(slot, b + 15, aa);
                 }
                 if (kept(j)) {
                     const int b = nkept * 18;
-                    tc_put(store, b, ul); tc_put(store, b + 3, ua); tc_put(store, b + 6, wl); tc_put(store, b + 9, wa);
-                    tc_put(store, b + 12, al); tc_put(store, b + 15, aa);
+                    vjp_slot_put(store, b, ul); vjp_slot_put(store, b + 3, ua); vjp_slot_put(store, b + 6, wl); vjp_slot_put(store, b + 9, wa);
+                    vjp_slot_put(store, b + 12, al); vjp_slot_put(store, b + 15, aa);
                     ++nkept;
                 }
                 V3 Iul, Iua, Iwl, Iwa, Ial, Iaa;
@@ -170,8 +167,8 @@ RTB_HD void tree_coriolis_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin
                 V3 fl = FL[j] + cl, fa = FA[j] + ca;
                 if (g.save_slot >= 0) {
                     const int b = g.save_slot * kTcSD + 18;
-                    fl = fl + tc_get(slot, b);
-                    fa = fa + tc_get(slot, b + 3);
+                    fl = fl + vjp_slot_get(slot, b);
+                    fa = fa + vjp_slot_get(slot, b + 3);
                 }
                 FL[j] = fl; FA[j] = fa;
                 cl = tc_zero(); ca = tc_zero();
@@ -181,7 +178,7 @@ RTB_HD void tree_coriolis_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin
                     const V3 ta = add_cross_pa(7, seg_r(g, rz(sn[j], cs[j], fa)), p, tl);
                     if (g.parent_slot >= 0) {
                         const int b = g.parent_slot * kTcSD + 18;
-                        tc_add(slot, b, tl); tc_add(slot, b + 3, ta);
+                        vjp_slot_add(slot, b, tl); vjp_slot_add(slot, b + 3, ta);
                     } else {
                         cl = tl; ca = ta;
                     }
@@ -207,19 +204,19 @@ RTB_HD void tree_coriolis_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin
                     V3 pbl = bl, pba = ba;
                     if (g.parent_slot >= 0) {
                         const int b = g.parent_slot * kTcSD;
-                        pbl = tc_get(slot, b); pba = tc_get(slot, b + 3);
+                        pbl = vjp_slot_get(slot, b); pba = vjp_slot_get(slot, b + 3);
                     }
                     const V3 p = tree_origin(false, g, slide(g, j));
                     xa = rz_t(sn[j], cs[j], seg_rt(g, pba));
                     xl = rz_t(sn[j], cs[j], seg_rt(g, add_cross_ap(7, pbl, pba, p)));
-                    t = pris ? -tcz(xa, FL[j]) : -(tcz(xl, FL[j]) + tcz(xa, FA[j]));
+                    t = pris ? -vjp_zcross(xa, FL[j]) : -(vjp_zcross(xl, FL[j]) + vjp_zcross(xa, FA[j]));
                 }
                 accq[j] = accq[j] + (jm_flip(g.jmeta) ? -t : t);
                 if (j == i) { if (pris) xl.z += 0.5; else xa.z += 0.5; }
                 FL[j] = xl; FA[j] = xa;
                 if (g.save_slot >= 0) {
                     const int b = g.save_slot * kTcSD;
-                    tc_put(slot, b, xl); tc_put(slot, b + 3, xa);
+                    vjp_slot_put(slot, b, xl); vjp_slot_put(slot, b + 3, xa);
                 }
                 bl = xl; ba = xa;
                 if (NG > 0) sched_fence();
@@ -241,15 +238,15 @@ RTB_HD void tree_coriolis_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin
                 if (kept(j)) {
                     --nkept;
                     const int b = nkept * 18;
-                    ul = tc_get(store, b); ua = tc_get(store, b + 3); wl = tc_get(store, b + 6); wa = tc_get(store, b + 9);
-                    al = tc_get(store, b + 12); aa = tc_get(store, b + 15);
+                    ul = vjp_slot_get(store, b); ua = vjp_slot_get(store, b + 3); wl = vjp_slot_get(store, b + 6); wa = vjp_slot_get(store, b + 9);
+                    al = vjp_slot_get(store, b + 12); aa = vjp_slot_get(store, b + 15);
                 }
                 V3 ubl = cul, uba = cua, wbl = cwl, wba = cwa, abl = cal, aba = caa;
                 if (g.save_slot >= 0) {
                     const int b = g.save_slot * kTcSD + 6;
-                    ubl = ubl + tc_get(slot, b); uba = uba + tc_get(slot, b + 3);
-                    wbl = wbl + tc_get(slot, b + 6); wba = wba + tc_get(slot, b + 9);
-                    abl = abl + tc_get(slot, b + 12); aba = aba + tc_get(slot, b + 15);
+                    ubl = ubl + vjp_slot_get(slot, b); uba = uba + vjp_slot_get(slot, b + 3);
+                    wbl = wbl + vjp_slot_get(slot, b + 6); wba = wba + vjp_slot_get(slot, b + 9);
+                    abl = abl + vjp_slot_get(slot, b + 12); aba = aba + vjp_slot_get(slot, b + 15);
                 }
                 if (j >= i) {
                     // the group's own force  I a + crf(u) I w + crf(w) I u
@@ -266,17 +263,17 @@ RTB_HD void tree_coriolis_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin
                 if (pris) {
                     uba = tc_zx(qdw, abl, uba);
                     wba = tc_zx(qdu, abl, wba);
-                    oqd = ubl.z + tcz(abl, wa);
-                    t = -((tcz(ua, ubl) + tcz(wa, wbl)) + tcz(aa, abl));
+                    oqd = ubl.z + vjp_zcross(abl, wa);
+                    t = -((vjp_zcross(ua, ubl) + vjp_zcross(wa, wbl)) + vjp_zcross(aa, abl));
                     xal = v3(__builtin_fma(-qdu, wa.y, __builtin_fma(-qdw, ua.y, al.x)), __builtin_fma(qdu, wa.x, __builtin_fma(qdw, ua.x, al.y)), al.z);
                     xaa = aa;
                 } else {
                     ubl = tc_zx(qdw, abl, ubl); uba = tc_zx(qdw, aba, uba);
                     wbl = tc_zx(qdu, abl, wbl); wba = tc_zx(qdu, aba, wba);
-                    oqd = uba.z + (tcz(abl, wl) + tcz(aba, wa));
+                    oqd = uba.z + (vjp_zcross(abl, wl) + vjp_zcross(aba, wa));
                     xal = v3(__builtin_fma(-qdu, wl.y, __builtin_fma(-qdw, ul.y, al.x)), __builtin_fma(qdu, wl.x, __builtin_fma(qdw, ul.x, al.y)), al.z);
                     xaa = v3(__builtin_fma(-qdu, wa.y, __builtin_fma(-qdw, ua.y, aa.x)), __builtin_fma(qdu, wa.x, __builtin_fma(qdw, ua.x, aa.y)), aa.z);
-                    t = -(((tcz(ul, ubl) + tcz(ua, uba)) + (tcz(wl, wbl) + tcz(wa, wba))) + (tcz(xal, abl) + tcz(xaa, aba)));
+                    t = -(((vjp_zcross(ul, ubl) + vjp_zcross(ua, uba)) + (vjp_zcross(wl, wbl) + vjp_zcross(wa, wba))) + (vjp_zcross(xal, abl) + vjp_zcross(xaa, aba)));
                 }
                 accq[j] = accq[j] + sigma * t;
                 accd[j] = accd[j] + oqd;
@@ -291,8 +288,8 @@ RTB_HD void tree_coriolis_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin
                     const V3 haa = add_cross_pa(7, seg_r(g, rz(sn[j], cs[j], aba)), p, hal);
                     if (g.parent_slot >= 0) {
                         const int b = g.parent_slot * kTcSD + 6;
-                        tc_add(slot, b, hul); tc_add(slot, b + 3, hua); tc_add(slot, b + 6, hwl); tc_add(slot, b + 9, hwa);
-                        tc_add(slot, b + 12, hal); tc_add(slot, b + 15, haa);
+                        vjp_slot_add(slot, b, hul); vjp_slot_add(slot, b + 3, hua); vjp_slot_add(slot, b + 6, hwl); vjp_slot_add(slot, b + 9, hwa);
+                        vjp_slot_add(slot, b + 12, hal); vjp_slot_add(slot, b + 15, haa);
                     } else {
                         cul = hul; cua = hua; cwl = hwl; cwa = hwa; cal = hal; caa = haa;
                         // ... and the joint run backwards: the state of the parent, group j - 1, from  X u_p = u - s qu,  X w_p = w - s qw,  X a_p
@@ -327,7 +324,8 @@ struct TreeCoriolisVjpParams {
 // then the branch slots and, for a compile-time group count, the kept states, [double][lane]
 inline __host__ __device__ int tree_coriolis_vjp_stride(int n, bool rt) { return (2 * n + (rt ? n : n * n)) | 1; }
 
-// One tile of 64 samples.  gq / gqd NULL: not stored.
+// One tile of 64 samples.  gq / gqd NULL: not stored.  The flush is vjp_tile.h's phase; the staging is this unit's own: with the staging
+// phases in its place UR5's adjoint measured 3 to 5 % slower (profiles/vjp_tile_refactor_ab.json).
 template <int NG>
 __device__ __forceinline__ void tree_coriolis_vjp_tile(const TreeCoriolisVjpParams &tp, ConstGroups groups, int n, int64_t tile,
                                                        const double *__restrict__ q, const double *__restrict__ qd, const double *__restrict__ gC,
@@ -335,14 +333,14 @@ __device__ __forceinline__ void tree_coriolis_vjp_tile(const TreeCoriolisVjpPara
 {
     const int stride = tree_coriolis_vjp_stride(n, NG == 0);
     double *slots = lds + kWave * stride;
-    const int64_t cfg0 = tile * kWave;
-    const int64_t left = tp.N - cfg0;
-    const int ncfg = left < kWave ? (int)left : kWave;
+    const VjpTile t = vjp_tile_of(tile, tp.N, n);
+    const int64_t cfg0 = t.cfg0;
+    const int ncfg = t.ncfg;
     const int nn = n * n;
-    const int count = ncfg * n, mcount = ncfg * nn;
+    const int count = t.count, mcount = t.mcount;
     const double *qg = q + cfg0 * n, *dg = qd + cfg0 * n, *mg = gC + cfg0 * nn;
     if constexpr (NG > 0) {
-        // all 2 NG + NG^2 coalesced loads in flight before the first LDS write (k_coriolis_vjp): unconditional -- an element past the ragged tail
+        // all 2 NG + NG^2 coalesced loads in flight before the first LDS write (vjp_tile.h tells why): unconditional -- an element past the ragged tail
         // reads element 0 of the tile -- and the zeros are selected afterwards
         double rq[NG], rd[NG], rm[NG * NG];
 #pragma unroll
@@ -389,31 +387,8 @@ __device__ __forceinline__ void tree_coriolis_vjp_tile(const TreeCoriolisVjpPara
         }
     }
     __syncthreads();
-    double *gout[2] = {gq ? gq + cfg0 * n : nullptr, gqd ? gqd + cfg0 * n : nullptr};
-    if constexpr (NG > 0) {
-        double r[2][NG];
-#pragma unroll
-        for (int k = 0; k < NG; ++k) {
-            const int f = lane + kWave * k;
-            const double *src = lds + (f / NG) * stride + (f % NG);
-            r[0][k] = src[0]; r[1][k] = src[NG];
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            if (!gout[a]) continue;          // wave-uniform
-#pragma unroll
-            for (int k = 0; k < NG; ++k) {
-                const int f = lane + kWave * k;
-                if (f < count) __builtin_nontemporal_store(r[a][k], gout[a] + f);
-            }
-        }
-    } else {
-        for (int f = lane; f < count; f += kWave) {
-            const double *src = lds + (f / n) * stride + (f % n);
-            if (gout[0]) gout[0][f] = src[0];
-            if (gout[1]) gout[1][f] = src[n];
-        }
-    }
+    double *const gout[2] = {gq ? gq + cfg0 * n : nullptr, gqd ? gqd + cfg0 * n : nullptr};
+    vjp_tile_flush<NG, true>(gout, t, n, stride, lane, lds);
 }
 
 // compile-time group count: one tile per single-wave workgroup, one wave per SIMD
@@ -440,18 +415,6 @@ __global__ __launch_bounds__(kWave) void k_tree_coriolis_vjp_rt(TreeCoriolisVjpP
 }
 
 #if RTB_HOST_SIDE
-namespace {
-
-template <class K>
-void tree_coriolis_vjp_go(K k, dim3 grid, size_t lds, hipStream_t s, const TreeCoriolisVjpParams &tp, const DevGroup *g, const double *q,
-                          const double *qd, const double *gC, double *gq, double *gqd)
-{
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, grid, dim3(kWave), lds, s, tp, g, q, qd, gC, gq, gqd);
-}
-
-}  // namespace
-
 // (declared in api.cpp, weakly: a library linked without this unit refuses the entry point instead of failing to load)
 int launch_tree_coriolis_vjp(const Tree *t, const DevGroup *groups, const double *q, const double *qd, int64_t N, const double *gC, double *gq,
                              double *gqd, hipStream_t s)
@@ -474,15 +437,15 @@ int launch_tree_coriolis_vjp(const Tree *t, const DevGroup *groups, const double
     if (lds > 160 * 1024) { set_error("tree_coriolis_vjp: tree needs more LDS than a CU has"); return RTBHIP_ELIMIT; }
     dim3 grid((unsigned)(rt && tiles > 65536 ? 65536 : tiles));      // the run-time-n kernel strides over the tiles
     switch (rt ? 0 : t->n) {
-    case 1: tree_coriolis_vjp_go(k_tree_coriolis_vjp<1>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
-    case 2: tree_coriolis_vjp_go(k_tree_coriolis_vjp<2>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
-    case 3: tree_coriolis_vjp_go(k_tree_coriolis_vjp<3>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
-    case 4: tree_coriolis_vjp_go(k_tree_coriolis_vjp<4>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
-    case 5: tree_coriolis_vjp_go(k_tree_coriolis_vjp<5>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
-    case 6: tree_coriolis_vjp_go(k_tree_coriolis_vjp<6>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
-    case 7: tree_coriolis_vjp_go(k_tree_coriolis_vjp<7>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
-    case 8: tree_coriolis_vjp_go(k_tree_coriolis_vjp<8>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
-    default: tree_coriolis_vjp_go(k_tree_coriolis_vjp_rt, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    case 1: vjp_go(k_tree_coriolis_vjp<1>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    case 2: vjp_go(k_tree_coriolis_vjp<2>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    case 3: vjp_go(k_tree_coriolis_vjp<3>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    case 4: vjp_go(k_tree_coriolis_vjp<4>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    case 5: vjp_go(k_tree_coriolis_vjp<5>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    case 6: vjp_go(k_tree_coriolis_vjp<6>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    case 7: vjp_go(k_tree_coriolis_vjp<7>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    case 8: vjp_go(k_tree_coriolis_vjp<8>, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
+    default: vjp_go(k_tree_coriolis_vjp_rt, grid, lds, s, tp, groups, q, qd, gC, gq, gqd); break;
     }
     note_launch((int)grid.x, kWave, (int)lds);
     hipError_t e = hipGetLastError();

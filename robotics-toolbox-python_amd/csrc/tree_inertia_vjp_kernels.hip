@@ -19,6 +19,7 @@
 // I/O as k_inertia_vjp: lane-major LDS tile of  q (n) | S (n (n + 1) / 2, packed: (j, i) at j (j + 1) / 2 + i)  doubles per row at an odd stride,
 // then the branch slots, [slot double][lane]; gq overwrites the q slots and leaves as contiguous non-temporal stores.
 #include "tree_kernels.h"
+#include "vjp_tile.h"
 
 namespace rtbhip {
 
@@ -26,11 +27,7 @@ namespace rtbhip {
 
 constexpr int kTreeInertiaVjpMaxGroups = 20;      // the forward kernel's built-in sizes (tree_dyn_kernels.hip: kTreeDynMax)
 
-RTB_HD double tiz(V3 a, V3 b) { return __builtin_fma(a.x, b.y, -(a.y * b.x)); }       // (a x b).z = ((0, 0, 1) x a) . b
 RTB_HD V3 ti_zero() { return v3(0, 0, 0); }
-template <class Slot> RTB_HD V3 ti_get(Slot &slot, int b) { return v3(slot(b + 0), slot(b + 1), slot(b + 2)); }
-template <class Slot> RTB_HD void ti_put(Slot &slot, int b, V3 v) { slot(b + 0) = v.x; slot(b + 1) = v.y; slot(b + 2) = v.z; }
-template <class Slot> RTB_HD void ti_add(Slot &slot, int b, V3 v) { slot(b + 0) += v.x; slot(b + 1) += v.y; slot(b + 2) += v.z; }
 // I [l; a] = [M l + a x h; I_bar a + h x l]  (symmetric: it is its own transpose)
 template <class G> RTB_HD void ti_inertia(const G &g, V3 l, V3 a, V3 &ol, V3 &oa)
 {
@@ -86,7 +83,7 @@ RTB_HD void tree_inertia_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin,
                     pal = ti_zero(); paa = ti_zero();
                 } else if (g.parent_slot >= 0) {
                     const int b = g.parent_slot * kTreeSlotDoubles;
-                    pal = ti_get(slot, b + 6); paa = ti_get(slot, b + 9);
+                    pal = vjp_slot_get(slot, b + 6); paa = vjp_slot_get(slot, b + 9);
                 } else {
                     pal = al; paa = aa;
                 }
@@ -98,7 +95,7 @@ RTB_HD void tree_inertia_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin,
                 else aa.z += qddj;
                 if (g.save_slot >= 0) {
                     const int b = g.save_slot * kTreeSlotDoubles;
-                    ti_put(slot, b + 6, al); ti_put(slot, b + 9, aa);
+                    vjp_slot_put(slot, b + 6, al); vjp_slot_put(slot, b + 9, aa);
                 }
                 AL[j] = al; AA[j] = aa;
                 V3 Ial, Iaa;
@@ -119,8 +116,8 @@ RTB_HD void tree_inertia_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin,
                 V3 fl = FL[j] + cl, fa = FA[j] + ca;
                 if (g.save_slot >= 0) {
                     const int b = g.save_slot * kTreeSlotDoubles + 12;
-                    fl = fl + ti_get(slot, b);
-                    fa = fa + ti_get(slot, b + 3);
+                    fl = fl + vjp_slot_get(slot, b);
+                    fa = fa + vjp_slot_get(slot, b + 3);
                 }
                 FL[j] = fl; FA[j] = fa;
                 cl = ti_zero(); ca = ti_zero();
@@ -130,7 +127,7 @@ RTB_HD void tree_inertia_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin,
                     const V3 ta = add_cross_pa(7, seg_r(g, rz(sn[j], cs[j], fa)), p, tl);
                     if (g.parent_slot >= 0) {
                         const int b = g.parent_slot * kTreeSlotDoubles + 12;
-                        ti_add(slot, b, tl); ti_add(slot, b + 3, ta);
+                        vjp_slot_add(slot, b, tl); vjp_slot_add(slot, b + 3, ta);
                     } else {
                         cl = tl; ca = ta;
                     }
@@ -153,12 +150,12 @@ RTB_HD void tree_inertia_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin,
                     V3 pbl = bl, pba = ba;
                     if (g.parent_slot >= 0) {
                         const int b = g.parent_slot * kTreeSlotDoubles;
-                        pbl = ti_get(slot, b); pba = ti_get(slot, b + 3);
+                        pbl = vjp_slot_get(slot, b); pba = vjp_slot_get(slot, b + 3);
                     }
                     const V3 p = tree_origin(false, g, slide(g, j));
                     xa = rz_t(sn[j], cs[j], seg_rt(g, pba));
                     xl = rz_t(sn[j], cs[j], seg_rt(g, add_cross_ap(7, pbl, pba, p)));
-                    t = pris ? -tiz(xa, FL[j]) : -(tiz(xl, FL[j]) + tiz(xa, FA[j]));
+                    t = pris ? -vjp_zcross(xa, FL[j]) : -(vjp_zcross(xl, FL[j]) + vjp_zcross(xa, FA[j]));
                 }
                 th[j] = t;
                 const double gt = sym(j, i);
@@ -166,7 +163,7 @@ RTB_HD void tree_inertia_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin,
                 FL[j] = xl; FA[j] = xa;
                 if (g.save_slot >= 0) {
                     const int b = g.save_slot * kTreeSlotDoubles;
-                    ti_put(slot, b, xl); ti_put(slot, b + 3, xa);
+                    vjp_slot_put(slot, b, xl); vjp_slot_put(slot, b + 3, xa);
                     for (int e = 12; e < 18; ++e) slot(b + e) = 0.0;      // the accumulator of abar for sweep 4
                 }
                 bl = xl; ba = xa;
@@ -188,14 +185,14 @@ RTB_HD void tree_inertia_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin,
                 V3 abl = cal, aba = caa;
                 if (g.save_slot >= 0) {
                     const int b = g.save_slot * kTreeSlotDoubles + 12;
-                    abl = abl + ti_get(slot, b); aba = aba + ti_get(slot, b + 3);
+                    abl = abl + vjp_slot_get(slot, b); aba = aba + vjp_slot_get(slot, b + 3);
                 }
                 // the group's own force  I a:  abar += I fbar
                 V3 tl, ta;
                 ti_inertia(g, fbl, fba, tl, ta);
                 abl = abl + tl; aba = aba + ta;
                 // the joint:  a = X a_p + s qdd  (qdd_j = 0 for j > i: X a_p = a)
-                const double t = pris ? -tiz(aa, abl) : -(tiz(al, abl) + tiz(aa, aba));
+                const double t = pris ? -vjp_zcross(aa, abl) : -(vjp_zcross(al, abl) + vjp_zcross(aa, aba));
                 acc[j] = acc[j] + sigma * (th[j] + t);
                 cal = ti_zero(); caa = ti_zero();
                 if (g.parent >= 0) {
@@ -204,7 +201,7 @@ RTB_HD void tree_inertia_vjp_lane(GroupsP groups, int n_rt, int nslots, InQ qin,
                     const V3 wa2 = add_cross_pa(7, seg_r(g, rz(sn[j], cs[j], aba)), p, wl2);
                     if (g.parent_slot >= 0) {
                         const int b = g.parent_slot * kTreeSlotDoubles + 12;
-                        ti_add(slot, b, wl2); ti_add(slot, b + 3, wa2);
+                        vjp_slot_add(slot, b, wl2); vjp_slot_add(slot, b + 3, wa2);
                     } else {
                         cal = wl2; caa = wa2;
                     }
@@ -227,7 +224,9 @@ struct TreeInertiaVjpParams {
 // LDS row of one sample: q (n) | S (n (n + 1) / 2) at an odd stride; then the branch slots, [slot double][lane]
 inline __host__ __device__ int tree_inertia_vjp_stride(int n) { return (n + n * (n + 1) / 2) | 1; }
 
-// One tile of 64 samples
+// One tile of 64 samples.  This unit keeps its own staging, fold (as vjp_tile.h's vjp_fold) and flush: with the phases in their place UR5's adjoint
+// measured 1.5 % slower in one build and 7 % faster in another, and with the flush phase alone the 13-group run-time-n form 0.3 % slower
+// (profiles/vjp_tile_refactor_ab.json).
 template <int NG>
 __device__ __forceinline__ void tree_inertia_vjp_tile(const TreeInertiaVjpParams &tp, ConstGroups groups, int n, int64_t tile, const double *__restrict__ q,
                                                       const double *__restrict__ gM, double *__restrict__ gq, double *lds, int lane)
@@ -248,7 +247,7 @@ __device__ __forceinline__ void tree_inertia_vjp_tile(const TreeInertiaVjpParams
         return row * stride + n + hi * (hi + 1) / 2 + lo;
     };
     if constexpr (NG > 0) {
-        // all NG + NG^2 coalesced loads in flight before the first LDS write (k_inertia_vjp): unconditional -- an element past the ragged tail
+        // all NG + NG^2 coalesced loads in flight before the first LDS write (vjp_tile.h tells why): unconditional -- an element past the ragged tail
         // reads element 0 of the tile -- and the zeros are selected afterwards
         double rq[NG], rm[NG * NG];
 #pragma unroll
@@ -339,18 +338,6 @@ __global__ __launch_bounds__(kWave) void k_tree_inertia_vjp_rt(TreeInertiaVjpPar
 }
 
 #if RTB_HOST_SIDE
-namespace {
-
-template <class K>
-void tree_inertia_vjp_go(K k, dim3 grid, size_t lds, hipStream_t s, const TreeInertiaVjpParams &tp, const DevGroup *g, const double *q, const double *gM,
-                         double *gq)
-{
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, grid, dim3(kWave), lds, s, tp, g, q, gM, gq);
-}
-
-}  // namespace
-
 // (declared in api.cpp, weakly: a library linked without this unit refuses the entry point instead of failing to load)
 int launch_tree_inertia_vjp(const Tree *t, const DevGroup *groups, const double *q, int64_t N, const double *gM, double *gq, hipStream_t s)
 {
@@ -365,15 +352,15 @@ int launch_tree_inertia_vjp(const Tree *t, const DevGroup *groups, const double 
     const bool rt = t->n > 8;
     dim3 grid((unsigned)(rt && tiles > 65536 ? 65536 : tiles));      // the run-time-n kernel strides over the tiles
     switch (rt ? 0 : t->n) {
-    case 1: tree_inertia_vjp_go(k_tree_inertia_vjp<1>, grid, lds, s, tp, groups, q, gM, gq); break;
-    case 2: tree_inertia_vjp_go(k_tree_inertia_vjp<2>, grid, lds, s, tp, groups, q, gM, gq); break;
-    case 3: tree_inertia_vjp_go(k_tree_inertia_vjp<3>, grid, lds, s, tp, groups, q, gM, gq); break;
-    case 4: tree_inertia_vjp_go(k_tree_inertia_vjp<4>, grid, lds, s, tp, groups, q, gM, gq); break;
-    case 5: tree_inertia_vjp_go(k_tree_inertia_vjp<5>, grid, lds, s, tp, groups, q, gM, gq); break;
-    case 6: tree_inertia_vjp_go(k_tree_inertia_vjp<6>, grid, lds, s, tp, groups, q, gM, gq); break;
-    case 7: tree_inertia_vjp_go(k_tree_inertia_vjp<7>, grid, lds, s, tp, groups, q, gM, gq); break;
-    case 8: tree_inertia_vjp_go(k_tree_inertia_vjp<8>, grid, lds, s, tp, groups, q, gM, gq); break;
-    default: tree_inertia_vjp_go(k_tree_inertia_vjp_rt, grid, lds, s, tp, groups, q, gM, gq); break;
+    case 1: vjp_go(k_tree_inertia_vjp<1>, grid, lds, s, tp, groups, q, gM, gq); break;
+    case 2: vjp_go(k_tree_inertia_vjp<2>, grid, lds, s, tp, groups, q, gM, gq); break;
+    case 3: vjp_go(k_tree_inertia_vjp<3>, grid, lds, s, tp, groups, q, gM, gq); break;
+    case 4: vjp_go(k_tree_inertia_vjp<4>, grid, lds, s, tp, groups, q, gM, gq); break;
+    case 5: vjp_go(k_tree_inertia_vjp<5>, grid, lds, s, tp, groups, q, gM, gq); break;
+    case 6: vjp_go(k_tree_inertia_vjp<6>, grid, lds, s, tp, groups, q, gM, gq); break;
+    case 7: vjp_go(k_tree_inertia_vjp<7>, grid, lds, s, tp, groups, q, gM, gq); break;
+    case 8: vjp_go(k_tree_inertia_vjp<8>, grid, lds, s, tp, groups, q, gM, gq); break;
+    default: vjp_go(k_tree_inertia_vjp_rt, grid, lds, s, tp, groups, q, gM, gq); break;
     }
     note_launch((int)grid.x, kWave, (int)lds);
     hipError_t e = hipGetLastError();

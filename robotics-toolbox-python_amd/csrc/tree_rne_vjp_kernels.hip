@@ -31,6 +31,7 @@
 // I/O as k_rne_vjp: the wave's (64 x n) blocks of q, qd, qdd and gtau are contiguous in memory, loaded coalesced into a lane-major LDS tile
 // (odd row stride); gq, gqd, gqdd overwrite the q, qd, qdd slots and leave the same way.
 #include "tree_kernels.h"
+#include "vjp_tile.h"
 
 namespace rtbhip {
 
@@ -38,11 +39,7 @@ namespace rtbhip {
 
 constexpr int kTreeVjpMaxGroups = 24;      // the forward kernel's built-in sizes
 
-RTB_HD double tvz(V3 a, V3 b) { return __builtin_fma(a.x, b.y, -(a.y * b.x)); }       // (a x b).z = ((0, 0, 1) x a) . b
 RTB_HD V3 tv_zero() { return v3(0, 0, 0); }
-template <class Slot> RTB_HD V3 tv_get(Slot &slot, int b) { return v3(slot(b + 0), slot(b + 1), slot(b + 2)); }
-template <class Slot> RTB_HD void tv_put(Slot &slot, int b, V3 v) { slot(b + 0) = v.x; slot(b + 1) = v.y; slot(b + 2) = v.z; }
-template <class Slot> RTB_HD void tv_add(Slot &slot, int b, V3 v) { slot(b + 0) += v.x; slot(b + 1) += v.y; slot(b + 2) += v.z; }
 // I [l; a] = [M l + a x h; I_bar a + h x l]  (symmetric: it is its own transpose)
 template <class G> RTB_HD void tv_inertia(const G &g, V3 l, V3 a, V3 &ol, V3 &oa)
 {
@@ -94,7 +91,7 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
                 pal = v3(-gravity.x, -gravity.y, -gravity.z); paa = tv_zero();
             } else if (g.parent_slot >= 0) {
                 const int b = g.parent_slot * kTreeSlotDoubles;
-                pvl = tv_get(slot, b); pva = tv_get(slot, b + 3); pal = tv_get(slot, b + 6); paa = tv_get(slot, b + 9);
+                pvl = vjp_slot_get(slot, b); pva = vjp_slot_get(slot, b + 3); pal = vjp_slot_get(slot, b + 6); paa = vjp_slot_get(slot, b + 9);
             } else {
                 pvl = vl; pva = va; pal = al; paa = aa;
             }
@@ -116,7 +113,7 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
             }
             if (g.save_slot >= 0) {
                 const int b = g.save_slot * kTreeSlotDoubles;
-                tv_put(slot, b, vl); tv_put(slot, b + 3, va); tv_put(slot, b + 6, al); tv_put(slot, b + 9, aa);
+                vjp_slot_put(slot, b, vl); vjp_slot_put(slot, b + 3, va); vjp_slot_put(slot, b + 6, al); vjp_slot_put(slot, b + 9, aa);
             }
             VL[j] = vl; VA[j] = va; AL[j] = al; AA[j] = aa;
             V3 Ial, Iaa, Ivl, Iva;
@@ -138,8 +135,8 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
             V3 fl = FL[j] + cl, fa = FA[j] + ca;
             if (g.save_slot >= 0) {
                 const int b = g.save_slot * kTreeSlotDoubles + 12;
-                fl = fl + tv_get(slot, b);
-                fa = fa + tv_get(slot, b + 3);
+                fl = fl + vjp_slot_get(slot, b);
+                fa = fa + vjp_slot_get(slot, b + 3);
             }
             FL[j] = fl; FA[j] = fa;
             cl = tv_zero(); ca = tv_zero();
@@ -149,7 +146,7 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
                 const V3 ta = add_cross_pa(7, seg_r(g, rz(sn[j], cs[j], fa)), p, tl);
                 if (g.parent_slot >= 0) {
                     const int b = g.parent_slot * kTreeSlotDoubles + 12;
-                    tv_add(slot, b, tl); tv_add(slot, b + 3, ta);
+                    vjp_slot_add(slot, b, tl); vjp_slot_add(slot, b + 3, ta);
                 } else {
                     cl = tl; ca = ta;
                 }
@@ -171,12 +168,12 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
                 V3 pbl = bl, pba = ba;
                 if (g.parent_slot >= 0) {
                     const int b = g.parent_slot * kTreeSlotDoubles;
-                    pbl = tv_get(slot, b); pba = tv_get(slot, b + 3);
+                    pbl = vjp_slot_get(slot, b); pba = vjp_slot_get(slot, b + 3);
                 }
                 const V3 p = tree_origin(false, g, slide(g));
                 xa = rz_t(sn[j], cs[j], seg_rt(g, pba));
                 xl = rz_t(sn[j], cs[j], seg_rt(g, add_cross_ap(7, pbl, pba, p)));
-                t = pris ? -tvz(xa, FL[j]) : -(tvz(xl, FL[j]) + tvz(xa, FA[j]));
+                t = pris ? -vjp_zcross(xa, FL[j]) : -(vjp_zcross(xl, FL[j]) + vjp_zcross(xa, FA[j]));
             }
             th[j] = t;
             const double gt = gin(g.out_col);
@@ -184,7 +181,7 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
             FL[j] = xl; FA[j] = xa;
             if (g.save_slot >= 0) {
                 const int b = g.save_slot * kTreeSlotDoubles;
-                tv_put(slot, b, xl); tv_put(slot, b + 3, xa);
+                vjp_slot_put(slot, b, xl); vjp_slot_put(slot, b + 3, xa);
                 for (int e = 6; e < 18; ++e) slot(b + e) = 0.0;      // the accumulators of (vbar, abar) for sweep 4
             }
             bl = xl; ba = xa;
@@ -207,8 +204,8 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
             V3 vbl = cvl, vba = cva, abl = cal, aba = caa;
             if (g.save_slot >= 0) {
                 const int b = g.save_slot * kTreeSlotDoubles + 6;
-                vbl = vbl + tv_get(slot, b); vba = vba + tv_get(slot, b + 3);
-                abl = abl + tv_get(slot, b + 6); aba = aba + tv_get(slot, b + 9);
+                vbl = vbl + vjp_slot_get(slot, b); vba = vba + vjp_slot_get(slot, b + 3);
+                abl = abl + vjp_slot_get(slot, b + 6); aba = aba + vjp_slot_get(slot, b + 9);
             }
             // the group's own force  I a + crf(v) I v:  abar += I fbar;  vbar += I (crm(fbar) v) - crf(fbar) (I v)
             V3 tl, ta, Ivl, Iva;
@@ -224,16 +221,16 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
             if (pris) {
                 oqdd = abl.z;
                 vba = v3(__builtin_fma(-qdj, abl.y, vba.x), __builtin_fma(qdj, abl.x, vba.y), vba.z);      // vbar += qd crf(s) abar = qd [0; z x abar_l]
-                oqd = vbl.z + tvz(abl, va);
-                t = -(tvz(va, vbl) + tvz(aa, abl));
+                oqd = vbl.z + vjp_zcross(abl, va);
+                t = -(vjp_zcross(va, vbl) + vjp_zcross(aa, abl));
             } else {
                 oqdd = aba.z;
                 vbl = v3(__builtin_fma(-qdj, abl.y, vbl.x), __builtin_fma(qdj, abl.x, vbl.y), vbl.z);      // qd [z x abar_l; z x abar_a]
                 vba = v3(__builtin_fma(-qdj, aba.y, vba.x), __builtin_fma(qdj, aba.x, vba.y), vba.z);
-                oqd = vba.z + (tvz(abl, vl) + tvz(aba, va));
+                oqd = vba.z + (vjp_zcross(abl, vl) + vjp_zcross(aba, va));
                 const V3 xal = v3(__builtin_fma(-qdj, vl.y, al.x), __builtin_fma(qdj, vl.x, al.y), al.z);     // X a_p up to its z parts
                 const V3 xaa = v3(__builtin_fma(-qdj, va.y, aa.x), __builtin_fma(qdj, va.x, aa.y), aa.z);
-                t = -((tvz(vl, vbl) + tvz(va, vba)) + (tvz(xal, abl) + tvz(xaa, aba)));
+                t = -((vjp_zcross(vl, vbl) + vjp_zcross(va, vba)) + (vjp_zcross(xal, abl) + vjp_zcross(xaa, aba)));
             }
             const double d = slide(g);
             gq(col, sigma * (th[j] + t));
@@ -248,7 +245,7 @@ RTB_HD void tree_rne_vjp_lane(GroupsP groups, int n_rt, int nslots, V3 gravity, 
                 const V3 wa2 = add_cross_pa(7, seg_r(g, rz(sn[j], cs[j], aba)), p, wl2);
                 if (g.parent_slot >= 0) {
                     const int b = g.parent_slot * kTreeSlotDoubles + 6;
-                    tv_add(slot, b, ul); tv_add(slot, b + 3, ua); tv_add(slot, b + 6, wl2); tv_add(slot, b + 9, wa2);
+                    vjp_slot_add(slot, b, ul); vjp_slot_add(slot, b + 3, ua); vjp_slot_add(slot, b + 6, wl2); vjp_slot_add(slot, b + 9, wa2);
                 } else {
                     cvl = ul; cva = ua; cal = wl2; caa = wa2;
                 }
@@ -270,7 +267,7 @@ struct TreeVjpParams {
 inline __host__ __device__ int tree_vjp_stride(int n) { return (4 * n) | 1; }
 
 // One tile of 64 samples.  qd / qdd NULL: zeros, not read.  gq / gqd / gqdd NULL: not stored (the lane body forms all three gradients either way:
-// they share the four sweeps).
+// they share the four sweeps).  The staging and the flush are vjp_tile.h's phases.
 template <int NG>
 __device__ __forceinline__ void tree_rne_vjp_tile(const TreeVjpParams &tp, ConstGroups groups, int n, int64_t tile, const double *__restrict__ q,
                                                   const double *__restrict__ qd, const double *__restrict__ qdd, const double *__restrict__ gtau,
@@ -278,44 +275,15 @@ __device__ __forceinline__ void tree_rne_vjp_tile(const TreeVjpParams &tp, Const
 {
     const int stride = tree_vjp_stride(n);
     double *slots = lds + kWave * stride;
-    const int64_t cfg0 = tile * kWave;
-    const int64_t left = tp.N - cfg0;
-    const int ncfg = left < kWave ? (int)left : kWave;
-    const int count = ncfg * n;
-    const double *gin[4] = {q + cfg0 * n, qd ? qd + cfg0 * n : nullptr, qdd ? qdd + cfg0 * n : nullptr, gtau + cfg0 * n};
-    if constexpr (NG > 0) {
-        // all 4 * NG coalesced loads in flight before the first LDS write (k_rne_vjp): unconditional -- an element past the ragged tail reads
-        // element 0 of the tile, an absent qd / qdd reads q -- and the zeros are selected afterwards
-        double r[4][NG];
-#pragma unroll
-        for (int k = 0; k < NG; ++k) {
-            const int f = lane + kWave * k, fc = f < count ? f : 0;
-#pragma unroll
-            for (int a = 0; a < 4; ++a) r[a][k] = (gin[a] ? gin[a] : gin[0])[fc];
-        }
-        sched_fence();
-#pragma unroll
-        for (int k = 0; k < NG; ++k) {
-            const int f = lane + kWave * k;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-                if (!gin[a] || f >= count) r[a][k] = 0.0;
-        }
-#pragma unroll
-        for (int k = 0; k < NG; ++k) {
-            const int f = lane + kWave * k;
-            double *dst = lds + (f / NG) * stride + (f % NG);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) dst[a * NG] = r[a][k];
-        }
-    } else {
-        for (int f = lane; f < kWave * n; f += kWave) {
-            double *dst = lds + (f / n) * stride + (f % n);
-            for (int a = 0; a < 4; ++a) dst[a * n] = (gin[a] && f < count) ? gin[a][f] : 0.0;
-        }
-    }
+    const VjpTile t = vjp_tile_of(tile, tp.N, n);
+    const int64_t at = t.cfg0 * n;
+    const double *const gin[4] = {q + at, qd ? qd + at : nullptr, qdd ? qdd + at : nullptr, gtau + at};
+    VjpCols<NG, 4, double> cols;
+    vjp_load_cols<NG, true>(gin, t, lane, cols);
+    sched_fence();
+    vjp_stage_cols<NG, true>(gin, t, n, stride, lane, cols, lds);
     __syncthreads();
-    if (lane < ncfg) {
+    if (lane < t.ncfg) {
         double *mine = lds + lane * stride;
         tree_rne_vjp_lane<NG>(groups, n, tp.nslots, v3(tp.grav[0], tp.grav[1], tp.grav[2]), [&](int c) { return mine[c]; },
                               [&](int c) { return mine[n + c]; }, [&](int c) { return mine[2 * n + c]; }, [&](int c) { return mine[3 * n + c]; },
@@ -323,32 +291,8 @@ __device__ __forceinline__ void tree_rne_vjp_tile(const TreeVjpParams &tp, Const
                               [&](int c, double v) { mine[2 * n + c] = v; }, [&](int i) -> double & { return slots[i * kWave + lane]; });
     }
     __syncthreads();
-    double *gout[3] = {gq ? gq + cfg0 * n : nullptr, gqd ? gqd + cfg0 * n : nullptr, gqdd ? gqdd + cfg0 * n : nullptr};
-    if constexpr (NG > 0) {
-        double r[3][NG];
-#pragma unroll
-        for (int k = 0; k < NG; ++k) {
-            const int f = lane + kWave * k;
-            const double *src = lds + (f / NG) * stride + (f % NG);
-#pragma unroll
-            for (int a = 0; a < 3; ++a) r[a][k] = src[a * NG];
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (!gout[a]) continue;          // wave-uniform
-#pragma unroll
-            for (int k = 0; k < NG; ++k) {
-                const int f = lane + kWave * k;
-                if (f < count) __builtin_nontemporal_store(r[a][k], gout[a] + f);
-            }
-        }
-    } else {
-        for (int f = lane; f < count; f += kWave) {
-            const double *src = lds + (f / n) * stride + (f % n);
-            for (int a = 0; a < 3; ++a)
-                if (gout[a]) gout[a][f] = src[a * n];
-        }
-    }
+    double *const gout[3] = {gq ? gq + at : nullptr, gqd ? gqd + at : nullptr, gqdd ? gqdd + at : nullptr};
+    vjp_tile_flush<NG, true>(gout, t, n, stride, lane, lds);
 }
 
 // compile-time group count (1..8): one tile per single-wave workgroup, one wave per SIMD
@@ -377,18 +321,6 @@ __global__ __launch_bounds__(kWave) void k_tree_rne_vjp_rt(TreeVjpParams tp, con
 }
 
 #if RTB_HOST_SIDE
-namespace {
-
-template <class K>
-void tree_vjp_go(K k, dim3 grid, size_t lds, hipStream_t s, const TreeVjpParams &tp, const DevGroup *g, const double *q, const double *qd,
-                 const double *qdd, const double *gtau, double *gq, double *gqd, double *gqdd)
-{
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, grid, dim3(kWave), lds, s, tp, g, q, qd, qdd, gtau, gq, gqd, gqdd);
-}
-
-}  // namespace
-
 // (declared in api.cpp, weakly: a library linked without this unit refuses the entry point instead of failing to load)
 int launch_tree_rne_vjp(const Tree *t, const DevGroup *groups, const double *q, const double *qd, const double *qdd, int64_t N, const double *grav3,
                         const double *gtau, double *gq, double *gqd, double *gqdd, hipStream_t s)
@@ -405,15 +337,15 @@ int launch_tree_rne_vjp(const Tree *t, const DevGroup *groups, const double *q, 
     const bool rt = t->n > 8;
     dim3 grid((unsigned)(rt && tiles > 65536 ? 65536 : tiles));      // the run-time-n kernel strides over the tiles
     switch (rt ? 0 : t->n) {
-    case 1: tree_vjp_go(k_tree_rne_vjp<1>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
-    case 2: tree_vjp_go(k_tree_rne_vjp<2>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
-    case 3: tree_vjp_go(k_tree_rne_vjp<3>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
-    case 4: tree_vjp_go(k_tree_rne_vjp<4>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
-    case 5: tree_vjp_go(k_tree_rne_vjp<5>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
-    case 6: tree_vjp_go(k_tree_rne_vjp<6>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
-    case 7: tree_vjp_go(k_tree_rne_vjp<7>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
-    case 8: tree_vjp_go(k_tree_rne_vjp<8>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
-    default: tree_vjp_go(k_tree_rne_vjp_rt, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    case 1: vjp_go(k_tree_rne_vjp<1>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    case 2: vjp_go(k_tree_rne_vjp<2>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    case 3: vjp_go(k_tree_rne_vjp<3>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    case 4: vjp_go(k_tree_rne_vjp<4>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    case 5: vjp_go(k_tree_rne_vjp<5>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    case 6: vjp_go(k_tree_rne_vjp<6>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    case 7: vjp_go(k_tree_rne_vjp<7>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    case 8: vjp_go(k_tree_rne_vjp<8>, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
+    default: vjp_go(k_tree_rne_vjp_rt, grid, lds, s, tp, groups, q, qd, qdd, gtau, gq, gqd, gqdd); break;
     }
     note_launch((int)grid.x, kWave, (int)lds);
     hipError_t e = hipGetLastError();

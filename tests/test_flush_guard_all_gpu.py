@@ -970,13 +970,13 @@ def _mat_vjp_inputs(kind, name, n):
 def _tree_slots_kept(parents):
     """(branch slots, kept groups) of a group table, restated: a group whose parent is not the group in front of it reads the parent's state through a
     slot, one slot per such parent (csrc/tree.cpp:94-101); the adjoint keeps the state of group j unless group j + 1 hangs directly off it
-    (csrc/tree_coriolis_vjp_kernels.hip:97, 466-468)"""
+    (csrc/tree_coriolis_vjp_kernels.hip: `kept` in tree_coriolis_vjp_lane, `nkept` in launch_tree_coriolis_vjp)"""
     n = len(parents)
     return len({p for j, p in enumerate(parents) if p >= 0 and p != j - 1}), sum(1 for j in range(n) if j + 1 >= n or parents[j + 1] != j)
 
 
 def _tree_coriolis_vjp_lds(n, nslots, nkept, rt):
-    """csrc/tree_coriolis_vjp_kernels.hip:328, 469-471: q | qd | gC (one row of it in the run-time-n form) at an odd stride, 24 doubles per branch
+    """csrc/tree_coriolis_vjp_kernels.hip: tree_coriolis_vjp_stride, `lds_of` in launch_tree_coriolis_vjp: q | qd | gC (one row of it in the run-time-n form) at an odd stride, 24 doubles per branch
     slot, and in the register form 18 per kept group"""
     return 64 * 8 * (((2 * n + (n if rt else n * n)) | 1) + 24 * nslots + (0 if rt else 18 * nkept))
 
@@ -987,7 +987,7 @@ def _ladder8():
     keeps the links in the order given (a depth-first numbering cannot produce this table: there a group that does not hang off the one in front of
     it follows a leaf).  6 branch slots and 7 kept groups: the register form of rtbhip_tree_coriolis_vjp would ask for
     64 * 8 * (81 + 24 * 6 + 18 * 7) = 179712 bytes > 160 KB, so launch_tree_coriolis_vjp serves it with the run-time-n form,
-    64 * 8 * (25 + 24 * 6) = 86528 bytes (csrc/tree_coriolis_vjp_kernels.hip:472).  One prismatic and one flipped joint."""
+    64 * 8 * (25 + 24 * 6) = 86528 bytes (csrc/tree_coriolis_vjp_kernels.hip: `rt` in launch_tree_coriolis_vjp).  One prismatic and one flipped joint."""
     from rtbhip import ET, ETS, Link, ERobot
     rng = _rng("ladder8")
     axes, flips = ("Rz", "Ry", "Rx", "tz", "Rz", "Ry", "Rx", "Rz"), (False, False, True, False, False, False, True, False)
@@ -1075,7 +1075,7 @@ def _inertia_vjp(name, tree):
             rob = _mat_dh_robot(name)
             n, h, fn = rob.n, rob._dyn_handle(), "rtbhip_inertia_vjp"
             q, _, g = _mat_vjp_inputs("inertia vjp", name, n)
-            # csrc/inertia_vjp_kernels.hip:186, 328: q (n) | the folded gM (n (n + 1) / 2) at an odd stride, the register and the run-time-n form alike
+            # csrc/inertia_vjp_kernels.hip: inertia_vjp_stride, `lds` in launch_inertia_vjp: q (n) | the folded gM (n (n + 1) / 2) at an odd stride, the register and the run-time-n form alike
             launch = lambda N: (_tiles(N), 64 * 8 * ((n + n * (n + 1) // 2) | 1))
         return Case(fn, {"q": In(q), "gM": In(g)}, [O("gq", n)], lambda N, p, s: (h, p("q"), N, p("gM"), p("gq"), MEM, s),
                     ref={"gq": ref}, rows=rows, tol=VJP_TOL, launch=launch, keep=rob, second=second, tol2=tol2)
@@ -1143,7 +1143,7 @@ def _coriolis_vjp(name, subset, tree, lds=None):
             n, h, fn = rob.n, rob._dyn_handle(), "rtbhip_coriolis_vjp"
             q, qd, g = _mat_vjp_inputs("coriolis vjp", name, n)
             rows, second, tol2 = None, None, None
-            rt = n > 7          # csrc/coriolis_vjp_kernels.hip:246, 255, 399-400: q | qd | gC at an odd stride; beyond kCoriolisVjpRegMax one row of gC per pass
+            rt = n > 7          # csrc/coriolis_vjp_kernels.hip: kCoriolisVjpRegMax, coriolis_vjp_stride, `rt` and `lds` in launch_coriolis_vjp: q | qd | gC at an odd stride; beyond kCoriolisVjpRegMax one row of gC per pass
             launch = lambda N: (_tiles(N), 64 * 8 * ((2 * n + (n if rt else n * n)) | 1))
             ref = dict(zip(("gq", "gqd"), _coriolis_vjp_ref(name, False)))
         return Case(fn, {"q": In(q), "qd": In(qd), "gC": In(g)}, [O("gq", n), O("gqd", n)],

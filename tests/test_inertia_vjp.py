@@ -136,7 +136,7 @@ def test_the_oracle_is_a_hundred_times_finer_than_the_bound(name):
         assert err <= 1e-11
 
 
-BIG_ANGLE = 2.0 ** 21 + 0.25          # beyond 2^20: the wave of such a lane takes the library's sine and cosine (csrc/inertia_vjp_kernels.hip:48, tree_trig)
+BIG_ANGLE = 2.0 ** 21 + 0.25          # beyond 2^20: the wave of such a lane takes the library's sine and cosine (csrc/inertia_vjp_kernels.hip: rne_trig in inertia_vjp_lane; tree_trig)
 BIG_H = 2.0 ** -10                    # q +- h and q +- 2 h are exact doubles at that magnitude (one ulp is 2^-31); at h = 1e-3 they are not, six digits lost
 
 
@@ -430,7 +430,7 @@ def test_nonfinite_and_huge_joint_values_stay_in_their_row(name):
     comp = _composition(rb, *_dev(torch, q, g)).cpu().numpy()
     scale = _scale(name)
     assert np.isfinite(clean).all() and float(np.abs(clean - comp).max()) <= 2e-9 * scale
-    always_library = _is_tree(rb) and rb.n > 8          # csrc/tree_inertia_vjp_kernels.hip:57-63
+    always_library = _is_tree(rb) and rb.n > 8          # csrc/tree_inertia_vjp_kernels.hip: the NG = 0 branch of tree_inertia_vjp_lane
     rows = np.arange(N)
 
     def check(what, got, row, depends, exact):
