@@ -221,8 +221,20 @@ struct TreeInertiaVjpParams {
     int64_t N;
 };
 
-// LDS row of one sample: q (n) | S (n (n + 1) / 2) at an odd stride; then the branch slots, [slot double][lane]
-inline __host__ __device__ int tree_inertia_vjp_stride(int n) { return (n + n * (n + 1) / 2) | 1; }
+// LDS row of one sample: q (n) | S (n (n + 1) / 2); then the branch slots, [slot double][lane].  An odd stride (conflict-free rows) while the tile
+// with its slots stays within a CU's 160 KiB: at 20 groups the row is 230 doubles, and with five branch slots (90) only the even stride fits --
+// 320 doubles per lane, exactly 160 KiB (as rne_vjp_stride gives up its odd stride at 32 joints)
+__host__ __device__ constexpr int tree_inertia_vjp_stride(int n, int nslots)
+{
+    const int row = n + n * (n + 1) / 2, odd = row | 1;
+    return (size_t)kWave * (odd + kTreeSlotDoubles * nslots) * sizeof(double) <= 160 * 1024 ? odd : row;
+}
+// The register forms take their stride with nslots = 0 (a compile-time constant), the launcher sizes the tile with the tree's nslots: the two
+// agree while the largest register form fits at the odd stride with every slot a tree of that size can have (n - 2: a slot needs a parent with
+// a child two or more groups on)
+constexpr int kTreeInertiaVjpRegMax = 8;
+static_assert(tree_inertia_vjp_stride(kTreeInertiaVjpRegMax, kTreeInertiaVjpRegMax - 2) == tree_inertia_vjp_stride(kTreeInertiaVjpRegMax, 0),
+              "a register form of k_tree_inertia_vjp would need the even stride: pass tp.nslots to tree_inertia_vjp_stride there too");
 
 // One tile of 64 samples.  This unit keeps its own staging, fold (as vjp_tile.h's vjp_fold) and flush: with the phases in their place UR5's adjoint
 // measured 1.5 % slower in one build and 7 % faster in another, and with the flush phase alone the 13-group run-time-n form 0.3 % slower
@@ -231,7 +243,8 @@ template <int NG>
 __device__ __forceinline__ void tree_inertia_vjp_tile(const TreeInertiaVjpParams &tp, ConstGroups groups, int n, int64_t tile, const double *__restrict__ q,
                                                       const double *__restrict__ gM, double *__restrict__ gq, double *lds, int lane)
 {
-    const int stride = tree_inertia_vjp_stride(n);
+    // (a register form always fits at the odd stride -- the static_assert above -- and keeps it a compile-time constant)
+    const int stride = tree_inertia_vjp_stride(n, NG > 0 ? 0 : tp.nslots);
     double *slots = lds + kWave * stride;
     const int64_t cfg0 = tile * kWave;
     const int64_t left = tp.N - cfg0;
@@ -347,9 +360,9 @@ int launch_tree_inertia_vjp(const Tree *t, const DevGroup *groups, const double 
     if (tiles > 0x7fffffff) { set_error("tree_inertia_vjp: batch too large for one launch"); return RTBHIP_ELIMIT; }
     TreeInertiaVjpParams tp;
     tp.n = t->n; tp.nslots = t->nslots; tp.N = N;
-    const size_t lds = (size_t)kWave * (tree_inertia_vjp_stride(t->n) + kTreeSlotDoubles * t->nslots) * sizeof(double);
+    const size_t lds = (size_t)kWave * (tree_inertia_vjp_stride(t->n, t->nslots) + kTreeSlotDoubles * t->nslots) * sizeof(double);
     if (lds > 160 * 1024) { set_error("tree_inertia_vjp: tree needs more LDS than a CU has"); return RTBHIP_ELIMIT; }
-    const bool rt = t->n > 8;
+    const bool rt = t->n > kTreeInertiaVjpRegMax;
     dim3 grid((unsigned)(rt && tiles > 65536 ? 65536 : tiles));      // the run-time-n kernel strides over the tiles
     switch (rt ? 0 : t->n) {
     case 1: vjp_go(k_tree_inertia_vjp<1>, grid, lds, s, tp, groups, q, gM, gq); break;

@@ -13,6 +13,7 @@ import pytest
 
 import emu_harness
 import coriolis_vjp_cases as cases
+import vjp_census_cases as census
 from test_inertia_vjp_emu import dyn_handle, tree_handle
 
 ROOT = emu_harness.ROOT
@@ -75,6 +76,22 @@ def test_tree_lane_body_equals_the_oracle(lib, name):
     _check("tree", name, both, (rq, rd))
     assert np.array_equal(_run(lib.emu_tree_coriolis_vjp, tree_handle(rob), q, qd, g, which=(True, False))[0], both[0])
     assert np.array_equal(_run(lib.emu_tree_coriolis_vjp, tree_handle(rob), q, qd, g, which=(False, True))[1], both[1])
+
+
+CENSUS_DH = ["n4s", "n4m", "n6m", "n7s"] + sorted(census.STRUCTURED)          # register forms the zoo above leaves out; exact zeros and special angles
+
+
+@pytest.mark.parametrize("name", CENSUS_DH)
+def test_dh_lane_body_equals_the_oracle_on_the_census_robots(lib, name):
+    """the robots tests/vjp_census_cases.py adds for the device, where this driver instantiates their joint count"""
+    rb, q, qd, g, rq, rd = census.coriolis_dh_case(name)
+    _check("dh", name, _run(lib.emu_coriolis_vjp, dyn_handle(rb), q, qd, g), (rq, rd))
+
+
+@pytest.mark.parametrize("name", ["t2", "t4"])
+def test_tree_lane_body_equals_the_oracle_on_the_census_trees(lib, name):
+    rob, orc, q, qd, g, rq, rd = census.coriolis_tree_case(name)
+    _check("tree", name, _run(lib.emu_tree_coriolis_vjp, tree_handle(rob), q, qd, g), (rq, rd))
 
 
 @pytest.mark.parametrize("N", SIZES)

@@ -13,6 +13,7 @@ import pytest
 
 import emu_harness
 import inertia_vjp_cases as cases
+import vjp_census_cases as census
 
 ROOT = emu_harness.ROOT
 SRC = os.path.join(ROOT, "tests", "emu_inertia_vjp", "emu_inertia_vjp.cpp")
@@ -88,6 +89,26 @@ def test_tree_lane_body_equals_the_oracle(lib, name):
     rob, orc, q, g, ref = cases.tree_case(name)
     got = _run(lib.emu_tree_inertia_vjp, tree_handle(rob), q[:N], g[:N])
     err = cases.rel_err(got, ref[:N])
+    print("tree_inertia_vjp lane %s: rel err %.3e (|ref|max %.3g)" % (name, err, np.abs(ref).max()))
+    assert err <= cases.BOUND, (name, err)
+
+
+CENSUS_DH = ["n4s", "n4m", "n6m", "n7s"] + sorted(census.STRUCTURED)          # register forms the zoo above leaves out; exact zeros and special angles
+
+
+@pytest.mark.parametrize("name", CENSUS_DH)
+def test_dh_lane_body_equals_the_oracle_on_the_census_robots(lib, name):
+    """the robots tests/vjp_census_cases.py adds for the device, where this driver instantiates their joint count"""
+    rb, q, g, ref = census.inertia_dh_case(name)
+    err = cases.rel_err(_run(lib.emu_inertia_vjp, dyn_handle(rb), q, g), ref)
+    print("inertia_vjp lane %s: rel err %.3e (|ref|max %.3g)" % (name, err, np.abs(ref).max()))
+    assert err <= cases.BOUND, (name, err)
+
+
+@pytest.mark.parametrize("name", ["t2", "t4"])
+def test_tree_lane_body_equals_the_oracle_on_the_census_trees(lib, name):
+    rob, orc, q, g, ref = census.inertia_tree_case(name)
+    err = cases.rel_err(_run(lib.emu_tree_inertia_vjp, tree_handle(rob), q, g), ref)
     print("tree_inertia_vjp lane %s: rel err %.3e (|ref|max %.3g)" % (name, err, np.abs(ref).max()))
     assert err <= cases.BOUND, (name, err)
 

@@ -13,6 +13,7 @@ import pytest
 
 import emu_harness
 import rne_vjp_cases as cases
+import vjp_census_cases as census
 
 ROOT = emu_harness.ROOT
 SRC = os.path.join(ROOT, "tests", "emu_rne_vjp", "emu_rne_vjp.cpp")
@@ -57,6 +58,22 @@ N = 24
 @pytest.mark.parametrize("name", sorted(cases.ROBOTS))
 def test_lane_body_equals_the_oracle(lib, name):
     rb, q, qd, qdd, g, gravity, fext, ref = cases.case(name, N)
+    got = _run(lib, rb, q, qd, qdd, g)
+    for what, a, b in zip(("gq", "gqd", "gqdd"), got, ref):
+        err = cases.rel_err(a, b)
+        print("rne_vjp lane %s %s: rel err %.3e" % (name, what, err))
+        assert err <= cases.BOUND, (name, what, err)
+    assert cases.rel_err(got[2], cases.inertia_gqdd(rb, q, g)) <= cases.BOUND
+
+
+CENSUS_DH = ["n4s", "n4m", "n6m", "n7s"] + sorted(census.STRUCTURED)          # register forms the zoo above leaves out; exact zeros and special angles
+
+
+@pytest.mark.parametrize("name", CENSUS_DH)
+def test_lane_body_equals_the_oracle_on_the_census_robots(lib, name):
+    """the robots tests/vjp_census_cases.py adds for the device, where this driver instantiates their joint count: a host-side slip in those bodies
+    fails without a GPU"""
+    rb, q, qd, qdd, g, ref = census.rne_case(name)
     got = _run(lib, rb, q, qd, qdd, g)
     for what, a, b in zip(("gq", "gqd", "gqdd"), got, ref):
         err = cases.rel_err(a, b)

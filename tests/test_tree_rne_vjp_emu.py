@@ -13,6 +13,7 @@ import pytest
 
 import emu_harness
 import tree_rne_vjp_cases as cases
+import vjp_census_cases as census
 
 ROOT = emu_harness.ROOT
 SRC = os.path.join(ROOT, "tests", "emu_tree_rne_vjp", "emu_tree_rne_vjp.cpp")
@@ -73,6 +74,18 @@ def test_lane_body_equals_the_oracle(lib, name):
         err = cases.rel_err(a, b)
         print("tree_rne_vjp lane %s %s: rel err %.3e (|ref|max %.3g)" % (name, what, err, np.abs(b).max()))
         assert err <= cases.BOUND, (name, what, err)
+
+
+@pytest.mark.parametrize("name", ["t2", "t4"])
+def test_lane_body_equals_the_oracle_on_the_census_trees(lib, name):
+    """the 2- and 4-group trees tests/vjp_census_cases.py adds for the device: register forms the robots above leave out"""
+    rob, orc, q, qd, qdd, g, gravity, ref = census.tree_rne_case(name)
+    got = _run(lib, rob, q, qd, qdd, g, gravity)
+    for what, a, b in zip(("gq", "gqd", "gqdd"), got, ref):
+        err = cases.rel_err(a, b)
+        print("tree_rne_vjp lane %s %s: rel err %.3e (|ref|max %.3g)" % (name, what, err, np.abs(b).max()))
+        assert err <= cases.BOUND, (name, what, err)
+    assert cases.rel_err(got[2], cases.inertia_gqdd(orc, q, g)) <= cases.BOUND
 
 
 @pytest.mark.parametrize("name", cases.AUTO)
