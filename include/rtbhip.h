@@ -289,6 +289,26 @@ int rtbhip_ik_qp(rtbhip_chain_t chain, const double *Tep, int64_t N, const doubl
  * ik.cpp:293: nothing to reproduce there.) */
 int rtbhip_ik_target_base(int64_t base);
 
+/* IMPLICIT-FUNCTION ADJOINT of rtbhip_ik_lm -- the backward pass of q = ik_LM / ik_GN / ik_NR (Tep), in one launch; no reference counterpart.
+ * What is differentiated is the solution map of _angle_axis(fkine(q), Tep) = 0 (core/ik.cpp:241-286) on the rows a with a non-zero weight in
+ * we6, with the Jacobian of _ETS_jacob0 (core/methods.cpp:112-217): at a solution  J_a dq = nu_a  for the world-frame twist nu of the target
+ * (d t = nu_v, d R = [nu_w]x R), so a gradient gq (N, n) on q pulls back to
+ *     y_a = (J_a J_a^T + damping^2 I)^-1 J_a gq,     y = 0 on the other rows
+ * (minimum norm for a redundant arm; the positive weights drop out).  q (N, n) is what rtbhip_ik_lm wrote to q_out, Tep (N, 4, 4) its targets,
+ * success (N) its flags or NULL (= every row is a solution); we6 is a HOST pointer (NULL = all ones), every other array is DEVICE memory.
+ * Outputs, either may be NULL (then neither computed nor stored, but not both): gtwist (N, 6) = y;  gTep (N, 4, 4) = the tangent-space
+ * gradient at Tep: translation column y_v, rotation block 1/2 [y_w]x R_p, bottom row 0 (rtbhip_fkine_jacob_vjp fed with it, or any other
+ * pull-back of a pose gradient, recovers y).  A row with success == 0 gets zeros.  A row whose 6 x 6 system has a zero or non-finite pivot
+ * (a singular J_a with damping 0, a non-finite q) is left non-finite and touches no other row: nothing is repaired, `damping` is the remedy.
+ * Chains of 1..32 joints with jindex 0..n-1 (1..10 in registers, 11..32 through jacob0 in stream-ordered scratch, hipMallocAsync on `stream`);
+ * fp64.  N == 0 returns RTBHIP_OK without a launch.  RTBHIP_EINVAL: unknown chain handle, negative N, a NULL input with N > 0, gTep and gtwist
+ * both NULL, a chain without joints, a chain whose jindex is not 0..n-1, more used rows than joints (rtbhip_ik_lm's steps are then the
+ * least-squares ones, whose solution map this is not), a negative or non-finite damping.  RTBHIP_ELIMIT: a batch beyond one launch's tiles
+ * (2^31 - 1 tiles of 64 rows). */
+int rtbhip_ik_vjp(rtbhip_chain_t chain, const double *q, int64_t N, const double *Tep, const int32_t *success,
+                  const double *we6 /* host, or NULL = all ones */, double damping, const double *gq,
+                  double *gTep, double *gtwist, void *stream);
+
 /* The restart vector the device generator yields for (seed, target index, search index, joint):
  * uniform in [qlim_lo, qlim_hi).  Exposed so tests can hand the CPU oracle the same sequence. */
 int rtbhip_ik_restart(rtbhip_chain_t chain, uint64_t seed, int64_t target, int32_t search,

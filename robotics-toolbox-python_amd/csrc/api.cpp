@@ -8,6 +8,7 @@
 #include "frames_device.h"
 #include "tree_device.h"
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
@@ -663,6 +664,9 @@ __attribute__((weak)) int launch_coriolis_vjp(const Dyn *d, const DevLink *links
                                               double *gq, double *gqd, hipStream_t s);
 __attribute__((weak)) int launch_tree_coriolis_vjp(const Tree *t, const DevGroup *groups, const double *q, const double *qd, int64_t N,
                                                    const double *gC, double *gq, double *gqd, hipStream_t s);
+// ... and of the implicit-function adjoint of the inverse kinematics (ikgrad_kernels.hip), weak for the same reason
+__attribute__((weak)) int launch_ik_vjp(const Chain *c, const DevChain &dc, const double *q, int64_t N, const double *Tep, const int32_t *success,
+                                        int rows, double d2, const double *gq, double *gTep, double *gtwist, hipStream_t s);
 namespace {
 
 // rtbhip_rne_vjp / rtbhip_rne_vjp_f32: the gradient of a loss on rtbhip_rne's torques with respect to q, qd and qdd (k_rne_vjp)
@@ -1289,6 +1293,35 @@ int rtbhip_ik_qp(rtbhip_chain_t chain, const double *Tep, int64_t N, const doubl
     if (!(kj > 0.0) || !(ks > 0.0)) { set_error("ik_qp: kj and ks must be positive (Q must be positive definite)"); return RTBHIP_EINVAL; }
     return ik_entry(chain, Tep, N, q0, ilimit, slimit, tol, reject_jl, we6, kj, 5, 1, seed, kq, km, ps, pi, ks, q_out, success, iters, searches,
                     residual, mem, stream);
+}
+
+/* the gradient of a loss on rtbhip_ik_lm's q with respect to the targets (k_ik_vjp): device pointers only, a backward pass sees nothing else */
+int rtbhip_ik_vjp(rtbhip_chain_t chain, const double *q, int64_t N, const double *Tep, const int32_t *success, const double *we6, double damping,
+                  const double *gq, double *gTep, double *gtwist, void *stream)
+{
+    const char *fn = "ik_vjp";
+    const std::shared_ptr<Chain> c_owner = chain_from_handle(chain);
+    Chain *c = c_owner.get();
+    RTB_TRACE(fn);
+    if (!c) return refuse(fn, "unknown chain handle");
+    if (N < 0) return refuse(fn, "negative N");
+    if (N > 0 && (!q || !Tep || !gq)) return refuse(fn, "NULL input with N > 0");
+    if (N > 0 && !gTep && !gtwist) return refuse(fn, "gTep and gtwist are both NULL: there is nothing to compute");
+    if (c->n < 1) return refuse(fn, "chain has no joints");
+    if (c->q_width != c->n) return refuse(fn, "chain must use jindex 0..n-1 (as rtbhip_ik_lm, whose q_out this reads)");
+    int rows = 0, used = 0;
+    for (int r = 0; r < 6; ++r)
+        if (!we6 || we6[r] != 0.0) { rows |= 1 << r; ++used; }
+    if (used > c->n) return refuse(fn, "more used rows than joints: the solver's step is the least-squares one there, not differentiated here");
+    if (!(damping >= 0.0) || !std::isfinite(damping)) return refuse(fn, "damping must be finite and >= 0");
+    if (N == 0) return RTBHIP_OK;
+    if ((N + 63) / 64 > 0x7fffffff) return refuse(fn, "batch too large for one launch", RTBHIP_ELIMIT);
+    if (!launch_ik_vjp) return refuse(fn, "not built into this library");
+    DeviceScope dscope;
+    RTB_TRY(dscope.enter_for(fn, q));
+    DevChain ops;
+    RTB_TRY(chain_device_ops(c, &ops, nullptr));
+    return launch_ik_vjp(c, ops, q, N, Tep, success, rows, damping * damping, gq, gTep, gtwist, (hipStream_t)stream);
 }
 
 int rtbhip_ik_restart(rtbhip_chain_t chain, uint64_t seed, int64_t target, int32_t search, double *q_n)

@@ -10,6 +10,7 @@
 // Roofline: HBM-bound by construction -- 8*qw bytes in, 128 + 48n bytes out per configuration
 // (520 B for the Panda), ~0.6 kflop of fp64 VALU + n sincos per configuration.
 #include "kin_reg.h"
+#include "kin_vjp.h"
 #include "diff_device.h"
 #include "servo_device.h"
 #include "diff_kernel.h"
@@ -939,21 +940,7 @@ static int launch_fleet_class(int cls, const std::vector<FleetEntry> &entries, i
 //           one suffix and one prefix running sum over the columns: O(n), the (n,6,n) Hessian is never formed.
 // Prismatic joints (w = 0, v = z) and flipped joints (the walk negated the column) need nothing extra: the finished columns carry both.
 // Every sum of two products is written out (kin_device.h: mix_pp and friends).
-template <class G>
-RTB_HD void vjp_pose_pullback(const Pose &P, int has_base, const double *base /* row-major 3x4 */, G g /* g(4 r + c): row r, column c of gT */, double (&w)[6])
-{
-#pragma clang fp contract(off)
-    double h[12];      // B_R^T gT (top three rows)
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            h[4 * i + c] = has_base ? dot3x(base[i], g(c), base[4 + i], g(4 + c), base[8 + i], g(8 + c)) : g(4 * i + c);
-    w[0] = h[3]; w[1] = h[7]; w[2] = h[11];
-    w[3] = (mix_pm(P.r10, h[8], P.r20, h[4]) + mix_pm(P.r11, h[9], P.r21, h[5])) + mix_pm(P.r12, h[10], P.r22, h[6]);
-    w[4] = (mix_pm(P.r20, h[0], P.r00, h[8]) + mix_pm(P.r21, h[1], P.r01, h[9])) + mix_pm(P.r22, h[2], P.r02, h[10]);
-    w[5] = (mix_pm(P.r00, h[4], P.r10, h[0]) + mix_pm(P.r01, h[5], P.r11, h[1])) + mix_pm(P.r02, h[6], P.r12, h[2]);
-}
+// (vjp_pose_pullback, the pull-back of gT onto (g_p ; m): kin_vjp.h)
 
 // The contraction.  J(r n + c) / G(r n + c): entry (r, c) of the row's finished Jacobian / of gJ; w = (g_p ; m) of the pose term (zeros without gT);
 // acc(k, x): gq_k += x (the receiver starts at zero; two joints may share a q column).  n is a compile-time constant in the register tile (the
@@ -990,52 +977,7 @@ RTB_HD void vjp_contract(int n, const double (&w)[6], JGet J, GGet G, Acc acc)
     }
 }
 
-// kin_flush in reverse: `cnt` consecutive rows of W values (W even, contiguous in global memory) into LDS rows of `stride` doubles, widened after
-// the load.  Lane l reads the pairs l, l + 64, ... of the run.  A pointer is only assumed aligned to its element (views of tensors are legal).
-template <class S>
-RTB_HD void vjp_fill(const S *__restrict__ src, int W, int cnt, double *rows, int stride, int lane)
-{
-    const int total = cnt * W;
-    int f = 2 * lane;
-    int r = f / W, e = f - r * W;
-    const int da = 128 / W, db = 128 - da * W;
-    for (; f < total; f += 128) {
-        double a, b;
-#if defined(__HIP_DEVICE_COMPILE__)
-        if constexpr (sizeof(S) == 4) {
-            typedef float v2f __attribute__((ext_vector_type(2)));
-            typedef v2f v2f_a4 __attribute__((aligned(4)));
-            const v2f v = *reinterpret_cast<const v2f_a4 *>(src + f);
-            a = v.x; b = v.y;
-        } else {
-            typedef double v2d __attribute__((ext_vector_type(2)));
-            typedef v2d v2d_a8 __attribute__((aligned(8)));
-            const v2d v = *reinterpret_cast<const v2d_a8 *>(src + f);
-            a = v.x; b = v.y;
-        }
-#else
-        a = src[f]; b = src[f + 1];
-#endif
-        double *dst = rows + r * stride + e;
-        dst[0] = a; dst[1] = b;
-        e += db; r += da;
-        if (e >= W) { e -= W; r += 1; }
-    }
-}
-// `cnt` staged rows of W values (any W >= 1) out as one contiguous run, one element per lane per instruction, rounded once
-template <class S>
-RTB_HD void vjp_flush(const double *rows, int stride, int W, int cnt, S *__restrict__ dst, int lane)
-{
-    const int total = cnt * W;
-    int f = lane;
-    int r = f / W, e = f - r * W;
-    const int da = kWave / W, db = kWave - da * W;
-    for (; f < total; f += kWave) {
-        dst[f] = (S)rows[r * stride + e];
-        e += db; r += da;
-        if (e >= W) { e -= W; r += 1; }
-    }
-}
+// (vjp_fill / vjp_flush, the row fill and flush of the LDS tiles: kin_vjp.h)
 
 // One register-resident tile: the walk of k_kin_reg (reg_compute: P and the finished Jacobian in registers), then the contraction in registers --
 // nothing of T, J or H goes to memory.  gT rows (one round of 64), gJ rows (rounds of kJRound lanes, contracted inside their round straight from

@@ -5,7 +5,7 @@ Imported by rtbhip/et.py only when a call's q is a CUDA tensor with requires_gra
 dependency of this module alone.  One Function: its forward is the ordinary call (gradients are off inside a Function's forward, so the
 front end takes the path it always took), its backward one launch of rtbhip_fkine_jacob_vjp(_f32) on the current stream -- for fkine_jacob0
 both outputs hang off one node, so a loss on T and J costs one backward launch.  The backward is not itself differentiable (no double
-backward).  Not differentiable at all, and unchanged: jacobe, frame=1, packed=True, out=, hessian0, the IK solvers.
+backward).  Not differentiable at all, and unchanged: jacobe, frame=1, packed=True, out=, hessian0, the ikine_* / IK_QP / IK_* class solvers.
 
 Every link frame (rtbhip/et.py routes ETS.link_frames here, and with it the fkine_all of every robot class): _FramesVJP's backward is one launch of
 rtbhip_link_frames_vjp for all the frames of the walk, float64.
@@ -24,7 +24,12 @@ _InertiaVJP / _TreeInertiaVJP's backward is one launch of rtbhip_inertia_vjp / r
 gradient once and writes gq once.
 
 The Coriolis matrix (`coriolis(q, qd)`, the same robots, float64): _CoriolisVJP / _TreeCoriolisVJP's backward is one launch of rtbhip_coriolis_vjp /
-rtbhip_tree_coriolis_vjp, which returns the gradients of q and qd that autograd asks for (ctx.needs_input_grad) and no others."""
+rtbhip_tree_coriolis_vjp, which returns the gradients of q and qd that autograd asks for (ctx.needs_input_grad) and no others.
+
+The inverse kinematics (rtbhip/et.py routes ETS.ik_LM / ik_GN / ik_NR here for a float64 Tep that asks for a gradient, when the mask uses no more
+rows than the chain has joints): _IkVJP's forward is the ordinary solve, its backward one launch of rtbhip_ik_vjp -- the implicit-function
+theorem at the returned q, J_a dq = nu_a, so  g_nu_a = (J_a J_a^T + d^2 I)^-1 J_a g_q  -- which returns the tangent-space gradient at Tep.
+Rows that did not converge get zero; q0, the joint limits and the solver's own settings play no part."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -368,3 +373,36 @@ def differentiable_tree_coriolis(robot, q, qd):
     """ERobot.coriolis(q, qd) attached to the autograd graph of q and qd (robots numbered in group order): the backward pass is one launch of
     rtbhip_tree_coriolis_vjp"""
     return _TreeCoriolisVJP.apply(q, qd, robot)
+
+
+# ---------------------------------------------------------------- the inverse kinematics (ETS.ik_LM / ik_GN / ik_NR)
+class _IkVJP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Tep, ets, args, mask, damping):
+        ctx.set_materialize_grads(False)
+        _, q, ok, it, se, E = ets._ik(Tep, *args)          # the ordinary call (gradients are off in here), flavour 0
+        ctx.mark_non_differentiable(ok, it, se, E)
+        ctx.save_for_backward(q, Tep, ok)
+        ctx.ets, ctx.mask, ctx.damping = ets, mask, damping
+        return q, ok, it, se, E
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gq, *_):
+        q, Tep, ok = ctx.saved_tensors
+        if gq is None:
+            return None, None, None, None, None
+        N, n = q.shape
+        Tq = Tep.detach().reshape(N, 16).contiguous()
+        g = gq.to(q.dtype).reshape(N, n).contiguous()      # (a .sum() loss delivers a stride-0 expanded tensor)
+        gT = torch.empty_like(Tq)
+        ptr = lambda x: C.c_void_p(x.data_ptr())
+        check(lib().rtbhip_ik_vjp(ctx.ets._handle(), ptr(q), N, ptr(Tq), ptr(ok), host_ptr(ctx.mask), ctx.damping, ptr(g), ptr(gT), None,
+                                  current_stream_ptr()))
+        return gT.reshape(Tep.shape), None, None, None, None
+
+
+def differentiable_ik(ets, Tep, args, grad_damping):
+    """ets._ik(Tep, *args) of the three C-loop solvers attached to the autograd graph of Tep -> (single, q, success, iterations, searches,
+    residual): the backward pass is one launch of rtbhip_ik_vjp; args[4] is the mask"""
+    return (Tep.dim() == 2,) + _IkVJP.apply(Tep, ets, args, small(args[4], 6), float(grad_damping))

@@ -1080,34 +1080,44 @@ class ETS:
                                            self._ptr(se, tm), self._ptr(E, tm), MEM_DEVICE if tm else MEM_HOST, self._stream(tm)))
         return single, qo, ok, it, se, E
 
+    def _ik_c(self, Tep, grad_damping, *args):
+        """_ik for the three C-loop solvers (flavour 0; args[4] is the mask).  A float64 CUDA Tep that asks for a gradient -- and a mask of no more
+        rows than the chain has joints, where the solution map is the minimum-norm one -- gets q attached to its autograd graph (rtbhip/autograd.py:
+        the backward pass is one launch of rtbhip_ik_vjp, damped by grad_damping); every other call is the ordinary one."""
+        if _lib.wants_grad(Tep) and _lib.is_f64(Tep) and (6 if args[4] is None else np.count_nonzero(small(args[4], 6))) <= self.n:
+            from . import autograd
+            return autograd.differentiable_ik(self, Tep, args, grad_damping)
+        return self._ik(Tep, *args)
+
     def ik_LM(self, Tep, q0=None, ilimit=30, slimit=100, tol=1e-6, mask=None, joint_limits=True, k=1.0,
-              method="chan", seed=0):
+              method="chan", seed=0, grad_damping=0.0):
         """Levenberg-Marquardt IK, loop resident on the GPU (reference ETS.ik_LM robot/ETS.py:2014-2170
         -> IK_LM_c core/fknm.cpp:394-525).  One Tep -> the reference's 5-tuple
-        (q, success, iterations, searches, residual); Tep (N,4,4) -> the same tuple of arrays."""
-        single, q, ok, it, se, E = self._ik(Tep, q0, ilimit, slimit, tol, mask, joint_limits, k, method, 0, seed)
+        (q, success, iterations, searches, residual); Tep (N,4,4) -> the same tuple of arrays.
+        grad_damping: the damping d of the backward pass when Tep is a CUDA tensor that requires grad (ignored otherwise)."""
+        single, q, ok, it, se, E = self._ik_c(Tep, grad_damping, q0, ilimit, slimit, tol, mask, joint_limits, k, method, 0, seed)
         if single:
             return q[0], int(ok[0]), int(it[0]), int(se[0]), float(E[0])
         return q, ok, it, se, E
 
     def ik_GN(self, Tep, q0=None, ilimit=30, slimit=100, tol=1e-6, mask=None, joint_limits=True, pinv=True,
-              pinv_damping=0.0, seed=0):
+              pinv_damping=0.0, seed=0, grad_damping=0.0):
         """Gauss-Newton IK on the GPU (reference ETS.ik_GN robot/ETS.py:2316-2442 -> IK_GN_c): same search loop,
         minimum-norm step of (J^T W J) dq = J^T W e.  `pinv=False` on a 6-joint arm is the same unique step;
         on a redundant arm the reference's QR branch returns a different (basic) solution of the singular system."""
-        single, q, ok, it, se, E = self._ik(Tep, q0, ilimit, slimit, tol, mask, joint_limits, 0.0, "gn", 0, seed)
+        single, q, ok, it, se, E = self._ik_c(Tep, grad_damping, q0, ilimit, slimit, tol, mask, joint_limits, 0.0, "gn", 0, seed)
         if single:
             return q[0], int(ok[0]), int(it[0]), int(se[0]), float(E[0])
         return q, ok, it, se, E
 
     def ik_NR(self, Tep, q0=None, ilimit=30, slimit=100, tol=1e-6, mask=None, joint_limits=True, pinv=True,
-              pinv_damping=0.0, seed=0):
+              pinv_damping=0.0, seed=0, grad_damping=0.0):
         """Newton-Raphson IK on the GPU (reference ETS.ik_NR robot/ETS.py:2172-2298 -> IK_NR_c): dq = J^+ e with
         the damped pseudo-inverse (core/ik.cpp:211-226).  Redundant arms need pinv (the reference forces it)."""
         if not pinv and self.n != 6:
             pinv = True                                       # ik.cpp:128-129
-        single, q, ok, it, se, E = self._ik(Tep, q0, ilimit, slimit, tol, mask, joint_limits,
-                                            float(pinv_damping) if pinv else 0.0, "nr", 0, seed)
+        single, q, ok, it, se, E = self._ik_c(Tep, grad_damping, q0, ilimit, slimit, tol, mask, joint_limits,
+                                              float(pinv_damping) if pinv else 0.0, "nr", 0, seed)
         if single:
             return q[0], int(ok[0]), int(it[0]), int(se[0]), float(E[0])
         return q, ok, it, se, E

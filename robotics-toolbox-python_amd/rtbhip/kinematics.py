@@ -118,9 +118,10 @@ class RobotKinematics:
 
     @staticmethod
     def _batch_only(kw):
-        """The one keyword this backend adds to the C-solver calls: `seed`, the key of the counter-based restart generator (the
-        reference draws from an unseeded std::rand, core/ik.cpp:293)."""
-        extra = set(kw) - {"seed"}
+        """The keywords this backend adds to the C-solver calls: `seed`, the key of the counter-based restart generator (the
+        reference draws from an unseeded std::rand, core/ik.cpp:293), and `grad_damping`, the damping of the backward pass for a Tep
+        that requires grad (rtbhip/autograd.py)."""
+        extra = set(kw) - {"seed", "grad_damping"}
         if extra:
             raise TypeError("unexpected keyword argument(s): %s" % ", ".join(sorted(extra)))
         return kw
