@@ -449,6 +449,34 @@ int rtbhip_tree_inertia_vjp(rtbhip_tree_t tree, const double *q, int64_t N, cons
 int rtbhip_tree_coriolis_vjp(rtbhip_tree_t tree, const double *q, const double *qd, int64_t N, const double *gC, double *gq, double *gqd,
                              int32_t mem, void *stream);
 
+/* OPERATIONAL-SPACE DYNAMICS from a supplied Jacobian, one launch: Dynamics.inertia_x (robot/Dynamics.py:924-1025), Dynamics.gravload_x
+ * (robot/Dynamics.py:1173-1290) and Asada's manipulability measure (robot/Robot.py:871-881).  q (N, n); J (N, 6, n) row-major: the Jacobian the
+ * caller wants inverted (the reference's jacob0_analytical for the first two, the geometric jacob0 for Asada).  With X = pinv(J), per row:
+ *     Mx (N, 6, 6) = X^T M X     M exactly what rtbhip_inertia / rtbhip_tree_inertia return (for a modified-DH chain with a prismatic first
+ *                                joint that is the reference's non-symmetric matrix)
+ *     Gx (N, 6)    = X^T g       g = rne(q, 0, 0) under grav3, in rtbhip_rne's (rtbhip_tree_rne's) convention.  (N, 6) for any n: the
+ *                                reference's trajectory branch allocates (m, n) for this 6-vector (:1273) and so only runs at n = 6; its
+ *                                single-q branch (:1260-1269) is what every row is here, as rtbhip_rne_base_wrench does for wbase
+ *     asada (N)    = lambda_min / lambda_max of the rows and columns of Mx that axes_mask selects (bit r = task-space row r; 63 all,
+ *                    7 translation, 56 rotation), the sub-block symmetrised first (the reference calls a general eig on a matrix that is
+ *                    symmetric up to rounding); 0 where J has not full rank
+ * Each output may be NULL (then neither computed nor stored), not all three.  grav3 is a HOST pointer, read only when Gx is given; every other
+ * array is DEVICE memory; the launch goes to `stream`.  X is applied as solves, never formed: n = 6 the inverse by LU with partial pivoting
+ * (pinv = inv at full rank), n > 6 J^T (J J^T)^-1 and n < 6 (J^T J)^-1 J^T by an LDL^T of the Gram matrix.
+ * RANK RULE (Asada only): with the eigenvalues of the 6 x 6 Gram matrix J J^T, a row is rank-deficient when
+ * lambda_min <= max(6, n) eps lambda_max -- the rounding floor of a Gram matrix; n < 6 is always deficient, as matrix_rank(J) < 6 is.
+ * NOT REPRODUCED: numpy's SVD-truncated pinv at a rank-deficient or non-finite J -- such a row of Mx / Gx is left non-finite or huge and touches
+ * no other row, nothing is repaired (rtbhip_ik_vjp's policy); matrix_rank's tolerance on singular values, which is finer than the rank rule by
+ * the band sigma_min / sigma_max of ~1e-15 .. ~4e-8 (where the reference's ratio is itself of the order of rounding: DESIGN.md);
+ * Dynamics.coriolis_x and accel_x (neither has a runnable definition for a general robot).
+ * Robots of 1..16 joints; trees numbered in group order; fp64.  N == 0 returns RTBHIP_OK without a launch.  RTBHIP_EINVAL: unknown handle,
+ * negative N, all three outputs NULL, a NULL q or J with N > 0, Gx without grav3, asada with an axes_mask that selects no row, a tree that is
+ * not numbered in group order.  RTBHIP_ELIMIT: more than 16 joints, a batch beyond one launch's tiles. */
+int rtbhip_opspace(rtbhip_dyn_t dyn, const double *q, const double *J, int64_t N, const double *grav3 /* host; may be NULL when Gx is NULL */,
+                   int32_t axes_mask, double *Mx, double *Gx, double *asada, void *stream);
+int rtbhip_tree_opspace(rtbhip_tree_t tree, const double *q, const double *J, int64_t N, const double *gravity3 /* host; may be NULL when Gx is NULL */,
+                        int32_t axes_mask, double *Mx, double *Gx, double *asada, void *stream);
+
 /* Mixed fleet (BASELINE config 5): n_chains independent chains, each with its own batch; one
  * launch walks all of them (block -> chain map).  q[c] is (N[c], q_width_c), T[c] (N[c],4,4),
  * J[c] (N[c],6,n_c).  The pointer tables themselves are HOST arrays. */

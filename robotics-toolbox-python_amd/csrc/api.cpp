@@ -667,7 +667,30 @@ __attribute__((weak)) int launch_tree_coriolis_vjp(const Tree *t, const DevGroup
 // ... and of the implicit-function adjoint of the inverse kinematics (ikgrad_kernels.hip), weak for the same reason
 __attribute__((weak)) int launch_ik_vjp(const Chain *c, const DevChain &dc, const double *q, int64_t N, const double *Tep, const int32_t *success,
                                         int rows, double d2, const double *gq, double *gTep, double *gtwist, hipStream_t s);
+// ... and of the operational-space dynamics (opspace_kernels.hip, tree_opspace_kernels.hip), weak for the same reason
+__attribute__((weak)) int launch_opspace(const Dyn *d, const DevLink *links, const double *q, const double *J, int64_t N, const double *grav3, int axes,
+                                         double *Mx, double *Gx, double *asada, hipStream_t s);
+__attribute__((weak)) int launch_tree_opspace(const Tree *t, const DevGroup *groups, const double *q, const double *J, int64_t N, const double *grav3,
+                                              int axes, double *Mx, double *Gx, double *asada, hipStream_t s);
 namespace {
+
+/* the argument checks rtbhip_opspace and rtbhip_tree_opspace share (n: the robot's joints); RTBHIP_OK with *go = false: nothing to launch */
+int opspace_check(const char *fn, int n, const double *q, const double *J, int64_t N, const double *grav3, int32_t axes_mask, const double *Mx,
+                  const double *Gx, const double *asada, bool *go)
+{
+    *go = false;
+    if (N < 0) return refuse(fn, "negative N");
+    if (!Mx && !Gx && !asada) return refuse(fn, "Mx, Gx and asada are all NULL: there is nothing to compute");
+    if (N > 0 && (!q || !J)) return refuse(fn, "NULL input with N > 0");
+    if (Gx && !grav3) return refuse(fn, "NULL gravity with a Gx output");
+    if (asada && (axes_mask & 63) == 0) return refuse(fn, "axes_mask selects no task-space row");
+    if (n < 1 || n > 16) return refuse(fn, "robots of 1..16 joints", RTBHIP_ELIMIT);
+    if (N == 0) return RTBHIP_OK;
+    if ((N + 7) / 8 > 0x7fffffff) return refuse(fn, "batch too large for one launch", RTBHIP_ELIMIT);
+    *go = true;
+    return RTBHIP_OK;
+}
+
 
 // rtbhip_rne_vjp / rtbhip_rne_vjp_f32: the gradient of a loss on rtbhip_rne's torques with respect to q, qd and qdd (k_rne_vjp)
 template <class R>
@@ -1556,6 +1579,48 @@ int rtbhip_tree_inertia_vjp(rtbhip_tree_t tree, const double *q, int64_t N, cons
     double *dgq = st.out(gq, bytes);
     RTB_TRY(st.status());
     return st.finish(launch_tree_inertia_vjp(t, groups, dq, N, dg, dgq, st.stream()));
+}
+
+/* operational-space dynamics from a supplied Jacobian (k_opspace / k_tree_opspace): device pointers only, like rtbhip_ik_vjp */
+int rtbhip_opspace(rtbhip_dyn_t dyn, const double *q, const double *J, int64_t N, const double *grav3, int32_t axes_mask, double *Mx, double *Gx,
+                   double *asada, void *stream)
+{
+    const char *fn = "opspace";
+    const std::shared_ptr<Dyn> d_owner = dyn_from_handle(dyn);
+    Dyn *d = d_owner.get();
+    RTB_TRACE(fn);
+    if (!d) return refuse(fn, "unknown dyn handle");
+    bool go = false;
+    RTB_TRY(opspace_check(fn, d->n, q, J, N, grav3, axes_mask, Mx, Gx, asada, &go));
+    if (!go) return RTBHIP_OK;
+    if (!launch_opspace) return refuse(fn, "not built into this library");
+    DeviceScope dscope;
+    RTB_TRY(dscope.enter_for(fn, q));
+    const DevLink *links = nullptr;
+    RTB_TRY(dyn_device_links(d, &links));
+    return launch_opspace(d, links, q, J, N, grav3, axes_mask, Mx, Gx, asada, (hipStream_t)stream);
+}
+
+int rtbhip_tree_opspace(rtbhip_tree_t tree, const double *q, const double *J, int64_t N, const double *grav3, int32_t axes_mask, double *Mx, double *Gx,
+                        double *asada, void *stream)
+{
+    const char *fn = "tree_opspace";
+    const std::shared_ptr<Tree> t_owner = tree_from_handle(tree);
+    Tree *t = t_owner.get();
+    RTB_TRACE(fn);
+    if (!t) return refuse(fn, "unknown tree handle");
+    bool go = false;
+    RTB_TRY(opspace_check(fn, t->n, q, J, N, grav3, axes_mask, Mx, Gx, asada, &go));
+    for (int j = 0; j < t->n; ++j)
+        if (jm_jq(t->groups[j].jmeta) != j)
+            return refuse(fn, "the robot is not numbered in group order (joint j of the q row must be moved by link group j)");
+    if (!go) return RTBHIP_OK;
+    if (!launch_tree_opspace) return refuse(fn, "not built into this library");
+    DeviceScope dscope;
+    RTB_TRY(dscope.enter_for(fn, q));
+    const DevGroup *groups = nullptr;
+    RTB_TRY(tree_device_groups(t, &groups));
+    return launch_tree_opspace(t, groups, q, J, N, grav3, axes_mask, Mx, Gx, asada, (hipStream_t)stream);
 }
 
 int rtbhip_tree_coriolis(rtbhip_tree_t tree, const double *q, const double *qd, int64_t N, double *Cm, int32_t mem, void *stream)

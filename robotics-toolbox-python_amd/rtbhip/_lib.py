@@ -158,6 +158,8 @@ SIGNATURES = {
     "rtbhip_coriolis": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp]),
     "rtbhip_coriolis_vjp": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _sc]),
     "rtbhip_accel": (C.c_int, [_u64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "rtbhip_opspace": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "rtbhip_tree_opspace": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "rtbhip_fleet_fkine_jacob": (C.c_int, [C.POINTER(_u64), _i32, C.POINTER(_vp), C.POINTER(_i64), _i32,
                                            C.POINTER(_vp), C.POINTER(_vp), _i32, _vp]),
     "rtbhip_fleet_fkine_jacob_packed": (C.c_int, [C.POINTER(_u64), _i32, C.POINTER(_vp), C.POINTER(_i64), _i32, C.POINTER(_vp), _i32, _vp]),

@@ -611,6 +611,17 @@ class DHRobot(RobotKinematics):
         check(lib().rtbhip_coriolis(self._dyn_handle(), ptr(arrs[0]), ptr(arrs[1]), N, ptr(Cm), mem, stream))
         return Cm[0] if single else Cm
 
+    # ---- what rtbhip.opspace (inertia_x, gravload_x, Asada's measure: one launch of rtbhip_opspace) asks of a robot class
+    def _opspace_call(self):
+        return lib().rtbhip_opspace, self._dyn_handle()
+
+    def _opspace_gravity(self, gravity):
+        return self._gravity_c(gravity)
+
+    def _opspace_ets(self, end):
+        self._refuse("the operational-space functions", end=end)
+        return self.ets()
+
     def accel(self, q, qd, torque, gravity=None):
         """Forward dynamics qdd = M^-1 (torque - rne(q, qd, 0)): (n,) or (N,n)
         (reference Dynamics.accel robot/Dynamics.py:424-509).  The solve is an LDL^T of the lower triangle of M as the recursion produces

@@ -561,6 +561,16 @@ class ERobot(RobotKinematics):
         check(lib().rtbhip_tree_coriolis(self._handle(), ptr(arrs[0]), ptr(arrs[1]), N, ptr(Cm), mem, stream))
         return Cm[0] if single else Cm
 
+    # ---- what rtbhip.opspace (inertia_x, gravload_x, Asada's measure: one launch of rtbhip_tree_opspace) asks of a robot class
+    def _opspace_call(self):
+        return lib().rtbhip_tree_opspace, self._handle()
+
+    def _opspace_gravity(self, gravity):
+        return self.gravity if gravity is None else np.asarray(gravity, dtype=np.float64).reshape(3)
+
+    def _opspace_ets(self, end):
+        return self._path(None, end)
+
     def accel(self, q, qd, torque, gravity=None):
         """Forward dynamics qdd = M(q)^-1 (torque - rne(q, qd, 0)): (n,) or (N,n) (reference Dynamics.accel robot/Dynamics.py:424-509).
         Differentiable with respect to CUDA q, qd and torque that require grad when the joints are numbered in group order (the default
