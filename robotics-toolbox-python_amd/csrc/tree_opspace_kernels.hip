@@ -41,6 +41,8 @@ int tree_ops_go(hipStream_t s, OpsParams op, int nslots, const DevGroup *g, cons
     const int per_row = L.stride + kTreeSlotDoubles * nslots;
     op.tile = ops_tile_rows(per_row);
     const size_t lds = (size_t)op.tile * per_row * sizeof(double);
+    // Not reachable with kOpsMaxJoints = 16: a tree of n groups has at most n - 2 branch slots (a slot needs a parent with a child two or more
+    // groups on), so a row is at most 265 + 18 * 14 = 517 doubles, which ops_tile_rows serves with 32 rows: 132352 bytes.  Kept for a larger limit.
     if (lds > 160 * 1024) { set_error("tree_opspace: the robot needs more LDS than a CU has"); return RTBHIP_ELIMIT; }
     const int64_t tiles = (op.N + op.tile - 1) / op.tile;
     if (tiles > 0x7fffffff) { set_error("tree_opspace: batch too large for one launch"); return RTBHIP_ELIMIT; }

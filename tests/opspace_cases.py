@@ -48,7 +48,7 @@ REFUSED = "hand4"
 NONSYMMETRIC = ("mdhp6",)
 
 
-def _with_prismatic(n, mdh, which, seed):
+def with_prismatic(n, mdh, which, seed):
     """dhc.random_robot's recipe with joint `which` prismatic"""
     rng = np.random.default_rng(seed)
     links = []
@@ -86,9 +86,9 @@ def robot(name):
     if name == "n16s":
         return dhc.random_robot(16, 0, 132)
     if name == "pris6":
-        return _with_prismatic(6, False, 2, 41)
+        return with_prismatic(6, False, 2, 41)
     if name == "mdhp6":
-        return _with_prismatic(6, True, 0, 43)
+        return with_prismatic(6, True, 0, 43)
     return _tree(name)[0]
 
 

@@ -45,7 +45,8 @@ the register form exists only with hand numbering: the register form's request 6
 two or more groups on), nkept <= n - 1 = 7.  A depth-first numbering keeps only leaves and has a slot per branching group, at most 162.  _ladder8
 (group j off group j - 2: 6 slots, 7 kept, 179712 bytes) is such a table; its row asserts the run-time-n request, 86528 bytes.
 
-The set of entry points is read from include/rtbhip.h (header_census): every `int rtbhip_*(..., int32_t mem, void *stream)`.  The ctypes table's
+The set of entry points is read from include/rtbhip.h (header_census): every `int rtbhip_*(..., int32_t mem, void *stream)`, and every
+`int rtbhip_*(... int64_t N ..., void *stream)` without a mem -- rtbhip_ik_vjp, rtbhip_opspace and rtbhip_tree_opspace, exactly.  The ctypes table's
 stream types (_sp, _si, _sc, ...) serve the families' refusal censuses and decide nothing here.
 
 Row-independence exceptions: none.  Every entry point of the table, IK included (q0 supplied, one search), returns for a row of a batch the bits
@@ -75,6 +76,14 @@ fraction of the bound it is held to:
     inertia_vjp            gq      3.4e-11  (8.1e-04)     tree_inertia_vjp    gq   7.0e-12  (1.9e-03)   against the composition  5.3e-15  (1.2e-07)
     coriolis_vjp           gq      9.3e-11  (1.4e-03)     tree_coriolis_vjp   gq   1.2e-11  (9.3e-04)   against the composition  3.6e-14  (1.1e-06)
                            gqd     3.2e-14  (1.6e-06)                         gqd  4.9e-15  (1.6e-06)   against the composition  1.4e-14  (8.5e-07)
+
+    opspace                Mx      3.0e-06  (0.43)        tree_opspace        Mx   5.8e-11  (0.035)       ik_vjp    gTep     7.2e-12  (2.7e-04)
+                           Gx      1.1e-08  (0.020)                           Gx   3.0e-12  (6.7e-03)                 gtwist   7.2e-12  (2.7e-04)
+                           asada   1.7e-14  (0.014)                           asada 5.8e-16 (4.6e-03)
+
+(the three entry points without a mem argument: puma560, panda, n9s, the general 16-joint chain p16s in tiles of 32 rows, UR5 and the ladder tree
+lad16_4 in tiles of 32 rows; the bound is K eps cond(J)^2 max|ref| per row, so the absolute figures are those of rows with cond(J) near 1e3;
+rows whose `success` is 0 return exact zeros.)
 
 (gq is held to a finite-difference stencil whose own error is some 1e-12 of the scale; gqd of the Coriolis pair to the exact linearity in qd, and
 the fused call agrees with the composition it replaces to a few ulp.)
@@ -1165,6 +1174,109 @@ for _r in ("UR5", "tree7", "tree8", "tree9"):
 row("tree_coriolis_vjp ladder8 both", "rtbhip_tree_coriolis_vjp", JIT0, _coriolis_vjp("ladder8", "both", True, lds=_tree_coriolis_vjp_lds(8, 6, 7, True)))
 
 
+# ------------------------------------------------------------------------------------------------ the entry points without a mem argument
+# rtbhip_opspace, rtbhip_tree_opspace and rtbhip_ik_vjp take device pointers only: (..., void *stream), no mem.  Inputs at NMAX DISTINCT rows (the
+# families' own cases repeat 16 or 24 rows cyclically).
+def _ops_zoo(name):
+    """(robot, tree?, gravity3, inertia, gravload, Jacobian of the robot's own path, bound factors (Mx, Gx, asada)) of a robot of tests/opspace_cases.py
+    or of tests/opspace_census_cases.py: the oracle and the bound K eps cond(J)^2 max|ref| per row of the module that names it"""
+    import opspace_cases as oc
+    import opspace_census_cases as occ
+    if name in occ.ALL:
+        jac = None if occ.is_tree(name) else (lambda q: oracle.jacob0(occ._chain(name), q))
+        return (occ.robot(name), occ.is_tree(name), occ.gravity3(name), lambda q: occ.inertia(name, q), lambda q: occ.gravload(name, q), jac, occ.K_OUT)
+    return (oc.robot(name), oc.is_tree(name), oc.gravity3(name), lambda q: oc.inertia(name, q), lambda q: oc.gravload(name, q), lambda q: oc.jacob0(name, q), (oc.K,) * 3)
+
+
+@functools.lru_cache(maxsize=None)
+def _ops_ref(name):
+    """(q, J, the oracle's rows): opspace_census_cases.draw_rows -- q ~ U(-3, 3), a draw replaced while cond(J) > 1e3, at most a third of them --
+    and opspace_cases.formula on all NMAX rows, once per robot"""
+    import opspace_census_cases as occ
+    rb, tree, g3, inertia, gravload, jac, k = _ops_zoo(name)
+    q, J, draws, replaced = occ.draw_rows("flush guard " + name, rb.n, NMAX, 8300 + sum(map(ord, name)), jac)
+    return q, J, occ.reference_of(q, J, inertia(q), gravload(q))
+
+
+def _opspace(name, want=("Mx", "Gx", "asada")):
+    """tests/test_opspace.py:153-166, tests/test_opspace_census.py: oracle.inertia_dh / erobot_inertia, oracle.rne_dh / erobot_rne and
+    numpy.linalg.inv / pinv / eig (opspace_cases.formula), per row K eps cond(J)^2 max|ref| (1 for the Asada ratio), mask 63.  The launch shape is
+    the restatement of ops_layout / ops_tile_rows in tests/opspace_census_cases.py: a tile of 32 rows means ceil(N / 32) workgroups"""
+    def build():
+        import opspace_cases as oc
+        import opspace_census_cases as occ
+        rb, tree, g3, _, _, _, kout = _ops_zoo(name)
+        q, J, ref = _ops_ref(name)
+        n = rb.n
+        fn, h = ("rtbhip_tree_opspace", rb._handle()) if tree else ("rtbhip_opspace", rb._dyn_handle())
+        g3 = np.ascontiguousarray(g3, dtype=np.float64)
+        w = occ.per_row(n, True, slots=occ.slots_of([r["parent"] for r in rb.group_table()])) if tree else occ.per_row(n, False, all(int(l.sigma) == 0 for l in rb.links))
+        tile = occ.tile_rows(w)
+        k = dict(zip(("Mx", "Gx", "asada"), kout))
+        cond2 = oc.EPS * ref["cond"] ** 2
+
+        def tol(nm, rows_ref, rows):
+            scale = np.ones(len(rows)) if nm == "asada" else np.abs(rows_ref).max(axis=1)
+            return (k[nm] * cond2[rows] * scale)[:, None]
+        return Case(fn, {"q": In(q), "J": In(J)}, [O("Mx", 36), O("Gx", 6), O("asada", 1)],
+                    lambda N, p, s: (h, p("q"), p("J"), N, _lib.host_ptr(g3), 63) + tuple(p(nm) if nm in want else None for nm in ("Mx", "Gx", "asada")) + (s,),
+                    ref={nm: _flat({"Mx": ref["Mx"], "Gx": ref["Gx"], "asada": ref["all"]}[nm]) for nm in want}, tol=tol,
+                    launch=lambda N: ((N + tile - 1) // tile, tile * w * 8), keep=(rb, g3),
+                    same_as=None if len(want) == 3 else _opspace(name))
+    return build
+
+
+# puma560: the LU path; panda: the static right Gram path; n9s: the run-time-n tail; p16s (general DH, 16 joints, joint 8 prismatic): a tile of 32
+# rows, ceil(N / 32) workgroups of 98560 bytes; UR5; lad16_4 (16 groups, four branch slots): a tile of 32 rows, 86272 bytes
+OPS_KN = {"puma560": {}, "panda": {}, "n9s": JIT0, "p16s": JIT0, "UR5": {}, "lad16_4": JIT0}
+for _r in OPS_KN:
+    _fn = "rtbhip_tree_opspace" if _r in ("UR5", "lad16_4") else "rtbhip_opspace"
+    row("%s %s" % (_fn[7:], _r), _fn, OPS_KN[_r], _opspace(_r))
+    row("%s %s Mx alone" % (_fn[7:], _r), _fn, OPS_KN[_r], _opspace(_r, ("Mx",)))
+
+
+@functools.lru_cache(maxsize=None)
+def _ik_vjp_inputs(name):
+    """tests/ik_vjp_cases.py:139-163 (inputs) at NMAX distinct rows: q ~ U(-3, 3), Tep = fkine(q) of the oracle, gq ~ U(-1, 1); a draw whose
+    cond(J_a J_a^T) exceeds 1e4 for the full or the translation mask is replaced, at most one third of them.  success: zeros on some seam rows"""
+    import ik_vjp_cases as kc
+    m = kc.model(name)
+    rng = _rng("ik_vjp", name)
+    cand = rng.uniform(-3.0, 3.0, (2 * NMAX, m.n))
+    Jc = m.jacob0(cand)
+    ok = np.array([max(kc._cond(Jc[i], None), kc._cond(Jc[i], kc.TRANS)) <= kc.COND_MAX for i in range(len(cand))])
+    keep = np.flatnonzero(ok)[:NMAX]
+    assert len(keep) == NMAX and 3 * int((~ok[:keep[-1] + 1]).sum()) <= keep[-1] + 1, (name, "more than one third of the draws replaced")
+    q, J = np.ascontiguousarray(cand[keep]), np.ascontiguousarray(Jc[keep])
+    Tep, gq = np.ascontiguousarray(m.fkine(q)), rng.uniform(-1.0, 1.0, (NMAX, m.n))
+    success = np.ones((NMAX, 1))
+    success[[0, 7, 8, 33, 63, 64, 100, 127]] = 0.0
+    assert {0, 7, 8, 63, 64, 127} <= set(SEAM_ROWS.tolist()) and success[128, 0] == 1.0
+    tw, gT = kc.reference(J, Tep, gq, None, 0.0)
+    tw[success[:, 0] == 0.0], gT[success[:, 0] == 0.0] = 0.0, 0.0          # a row that was not solved gets a zero gradient (tests/test_ik_vjp.py:424-436)
+    return m, q, Tep, gq, success, tw, gT
+
+
+def _ik_vjp(name, want=("gTep", "gtwist")):
+    """tests/test_ik_vjp.py:303-313, tests/ik_vjp_cases.py: oracle.jacob0 and numpy.linalg.solve restating the definition, all six rows used, no
+    damping; BOUND = 1e-9 of the row's largest reference magnitude.  we6 (NULL) is a host array and is not guarded"""
+    def build():
+        import ik_vjp_cases as kc
+        m, q, Tep, gq, success, tw, gT = _ik_vjp_inputs(name)
+        ets = m.ets
+        ref = {"gTep": _flat(gT), "gtwist": _flat(tw)}
+        return Case("rtbhip_ik_vjp", {"q": In(q), "Tep": In(Tep), "success": In(success, "int32"), "gq": In(gq)}, [O("gTep", 16), O("gtwist", 6)],
+                    lambda N, p, s: (ets._handle(), p("q"), N, p("Tep"), p("success"), None, 0.0, p("gq")) + tuple(p(nm) if nm in want else None for nm in ("gTep", "gtwist")) + (s,),
+                    ref={nm: ref[nm] for nm in want}, tol=lambda nm, w, rows: kc.BOUND * np.abs(w).max(axis=1)[:, None], launch=_grid_only, keep=(m, ets),
+                    same_as=None if len(want) == 2 else _ik_vjp(name))
+    return build
+
+
+for _r in ("panda", "n11"):          # panda: k_ik_vjp<7>, the register form; n11: k_ik_vjp_any, the run-time-n form on a Jacobian in stream-ordered scratch
+    for _w in (("gTep", "gtwist"), ("gTep",), ("gtwist",)):
+        row("ik_vjp %s %s" % (_r, "both" if len(_w) == 2 else _w[0] + " alone"), "rtbhip_ik_vjp", {} if _r == "panda" else JIT0, _ik_vjp(_r, _w))
+
+
 # ------------------------------------------------------------------------------------------------ the tests
 # entry points whose flush already has guard rows (or poisoned buffers) around every output, every row against the oracle: entry point -> that test
 ELSEWHERE = dict([(n, "test_kin_flush_guard_gpu.py::test_flush_writes_its_rows_and_leaves_the_guard_rows") for n in (
@@ -1176,17 +1288,25 @@ ELSEWHERE = dict([(n, "test_kin_flush_guard_gpu.py::test_flush_writes_its_rows_a
 NOT_COMPUTE = ("rtbhip_device_copy", "rtbhip_ik_restart")          # (..., mem / kind, stream) by shape, but no batch of rows is computed
 
 
-def header_census():
+MEMLESS = {"rtbhip_ik_vjp", "rtbhip_opspace", "rtbhip_tree_opspace"}          # compute entry points on device pointers only: (..., void *stream), no mem
+
+
+def header_census(mem_only=False):
     """every compute entry point, from include/rtbhip.h itself: each `int rtbhip_*(` declaration whose parameter list ends in
-    `int32_t mem, void *stream)`.  The ctypes table cannot opt an entry point out of this one by the type it gives the stream argument."""
+    `int32_t mem, void *stream)`, and (unless mem_only) each one on a robot's handle that has an `int64_t N` and ends in `void *stream)` without a
+    mem.  The ctypes
+    table cannot opt an entry point out of this one by the type it gives the stream argument, nor the declaration by leaving out mem."""
     import re
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rtbhip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
     hdr = re.sub(r"//[^\n]*", " ", hdr)
     found = set()
     for name, params in re.findall(r"\bint\s+(rtbhip_\w+)\s*\(([^;{}]*?)\)\s*;", hdr, flags=re.S):
-        if re.search(r"\bint32_t\s+mem\s*,\s*void\s*\*\s*stream\s*$", " ".join(params.split())):
+        flat = " ".join(params.split())
+        if re.search(r"\bint32_t\s+mem\s*,\s*void\s*\*\s*stream\s*$", flat):
             found.add(name)
+        elif not mem_only and re.search(r"\bint64_t\s+N\b", flat) and re.search(r"\bvoid\s*\*\s*stream\s*$", flat) and re.match(r"rtbhip_(chain|dyn|tree)_t\b", flat):
+            found.add(name)          # (a robot's handle first: rtbhip_shard_gather has an N and a stream too, and moves rows between ranks -- it computes none)
     return found - set(NOT_COMPUTE)
 
 
@@ -1217,6 +1337,12 @@ def test_every_compute_entry_point_is_in_the_table_or_guard_checked_elsewhere():
     assert declared >= types_census() and declared >= compute | vjp, sorted((types_census() | compute | vjp) - declared)
     assert declared <= set(_lib.SIGNATURES), sorted(declared - set(_lib.SIGNATURES))
     assert {"rtbhip_inertia_vjp", "rtbhip_tree_inertia_vjp", "rtbhip_coriolis_vjp", "rtbhip_tree_coriolis_vjp"} <= tabled
+    # the wider rule adds exactly the three entry points without a mem argument, and each has rows
+    with_mem = header_census(mem_only=True)
+    assert declared - with_mem == MEMLESS and not MEMLESS & with_mem, sorted(declared - with_mem)
+    assert MEMLESS <= tabled, "no table row for %s" % sorted(MEMLESS - tabled)
+    for fn in MEMLESS:
+        assert len({rid for rid, f, _, _ in ROWS if f == fn}) >= 4 and any("alone" in rid for rid, f, _, _ in ROWS if f == fn), fn
     here = os.path.dirname(os.path.abspath(__file__))
     for fn, where in ELSEWHERE.items():
         path, test = where.split("::")

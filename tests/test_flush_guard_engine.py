@@ -113,10 +113,13 @@ def test_a_row_swap_between_oracle_rows_fails_the_second_reference(monkeypatch, 
 
 
 def test_the_census_reads_the_header():
-    """every `int rtbhip_*(..., int32_t mem, void *stream)` of include/rtbhip.h has a row in the table or is guard-checked elsewhere, whatever type
+    """every `int rtbhip_*(..., int32_t mem, void *stream)` and every `int rtbhip_*(... int64_t N ..., void *stream)` of include/rtbhip.h has a row in the table or is guard-checked elsewhere, whatever type
     rtbhip/_lib.py gives its stream argument; a declaration the table does not know fails it"""
     eng.test_every_compute_entry_point_is_in_the_table_or_guard_checked_elsewhere()
     declared = eng.header_census()
     assert {"rtbhip_inertia_vjp", "rtbhip_tree_inertia_vjp", "rtbhip_coriolis_vjp", "rtbhip_tree_coriolis_vjp", "rtbhip_p_servo", "rtbhip_ik_qp"} <= declared
     assert not declared & {"rtbhip_device_copy", "rtbhip_ik_restart", "rtbhip_tree_create", "rtbhip_last_launch", "rtbhip_stream_probe"}
     assert not eng.types_census() >= declared          # the types rule alone misses the four (rtbhip/_lib.py: _si, _sc)
+    # the three entry points that take device pointers only (no mem argument) are declared compute entry points too, and only they are added
+    assert eng.MEMLESS == {"rtbhip_ik_vjp", "rtbhip_opspace", "rtbhip_tree_opspace"} <= declared
+    assert eng.header_census(mem_only=True) == declared - eng.MEMLESS and len(eng.header_census(mem_only=True)) == len(declared) - 3

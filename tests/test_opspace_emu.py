@@ -1,89 +1,36 @@
 """The operational-space dynamics on the CPU (no GPU needed): the lane body and the tile fill / flush phases of k_opspace / k_tree_opspace
-(csrc/opspace_device.h) compiled host-side by this test (tests/emu_opspace/emu_opspace.cpp, linked against tests/emu/libemu.so for the handle
-registry and the tree compiler) and held against the oracle of tests/opspace_cases.py -- oracle.inertia_dh / erobot_inertia, oracle.rne_dh /
+(csrc/opspace_device.h) compiled host-side for this test (tests/emu_opspace/emu_opspace.cpp, built by tests/opspace_emu_harness.py and linked
+against tests/emu/libemu.so for the handle registry and the tree compiler) and held against the oracle of tests/opspace_cases.py -- oracle.inertia_dh / erobot_inertia, oracle.rne_dh /
 erobot_rne, oracle.jacob0 and numpy.linalg.inv / pinv / eig -- at its bound, K eps cond(J)^2 max|ref| per row.  The device runs the same source
 through another compiler: tests/test_opspace.py."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import emu_harness
+import opspace_emu_harness as ops_emu
 import opspace_cases as cases
 
 ROOT = emu_harness.ROOT
-SRC = os.path.join(ROOT, "tests", "emu_opspace", "emu_opspace.cpp")
-SO = os.path.join(ROOT, "tests", "emu_opspace", "libemu_opspace.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "opspace_reference.npz")
-_vp, _u64, _i64, _i32 = C.c_void_p, C.c_uint64, C.c_int64, C.c_int32
 N = 70          # a full tile and a ragged one
 
 
 @pytest.fixture(scope="module")
 def lib():
-    base = emu_harness.lib()                     # libemu.so: the registry, tree.cpp (built if stale)
-    import __graft_entry__ as g
-    digest = g.source_digest(emu_harness._deps() + [SRC])
-    stamp = SO + ".stamp"
-    if not (os.path.exists(SO) and os.path.exists(stamp) and open(stamp).read().strip() == digest):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        emu_dir = os.path.dirname(emu_harness.EMU_SO)
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-O1", "-std=c++17", "-fPIC", "-x", "hip", "-w", "-I" + os.path.join(ROOT, "include"),
-                               "-shared", SRC, "-o", SO, "-L" + emu_dir, "-l:libemu.so", "-Wl,-rpath," + emu_dir])
-        open(stamp, "w").write(digest)
-    so = C.CDLL(SO)
-    so.emu_opspace.argtypes = [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]
-    so.emu_opspace_layout.argtypes, so.emu_opspace_layout.restype = [_i32, _i32, _i32, _vp], None
-    assert base is not None
-    return so
-
-
-_handles = {}
+    """tests/opspace_emu_harness.py builds the library (by parts, in parallel) when the digest of its sources changed"""
+    return ops_emu.lib()
 
 
 def _dyn_handle(name):
-    if name not in _handles:
-        rb = cases.robot(name)
-        L = np.ascontiguousarray(rb.L24())
-        h = _u64(0)
-        assert emu_harness.lib().rtbhip_dyn_create(emu_harness._p(L), rb.n, int(rb.mdh), C.byref(h)) == 0
-        _handles[name] = h.value
-    return _handles[name]
-
-
-def _groups(name):
-    from rtbhip._lib import rtbhip_tree_group
-    recs = cases.robot(name).group_table()
-    arr = (rtbhip_tree_group * len(recs))()
-    for k, r in enumerate(recs):
-        arr[k].parent, arr[k].kind, arr[k].flip, arr[k].jindex = r["parent"], r["kind"], r["flip"], r["jindex"]
-        arr[k].T[:] = list(np.ascontiguousarray(r["T"]).reshape(16))
-        arr[k].m = r["m"]
-        arr[k].h[:] = list(r["h"])
-        arr[k].I[:] = list(r["I"])
-    return arr, len(recs)
+    return ops_emu.dyn_handle(cases.robot(name))
 
 
 def _run(lib, name, q, J, axes=63, want=(True, True, True), fill=np.nan, rc=0):
     """-> [Mx (N, 6, 6), Gx (N, 6), asada (N)]; an output not wanted is handed over as NULL and comes back as the untouched buffer"""
-    p = emu_harness._p
-    q, J = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(J, dtype=np.float64)
-    n = q.shape[0]
-    out = [np.full((n, 6, 6), fill), np.full((n, 6), fill), np.full((n,), fill)]
-    ptrs = [p(o) if w else None for o, w in zip(out, want)]
-    g = cases.gravity3(name)
-    if cases.is_tree(name):
-        from rtbhip._lib import rtbhip_tree_group
-        arr, ng = _groups(name)
-        lib.emu_tree_opspace.argtypes = [C.POINTER(rtbhip_tree_group), _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]
-        got = lib.emu_tree_opspace(arr, ng, p(q), p(J), n, p(g), axes, *ptrs)
-    else:
-        got = lib.emu_opspace(_dyn_handle(name), p(q), p(J), n, p(g), axes, *ptrs)
-    assert got == rc, got
-    return out
+    return ops_emu.run(cases.robot(name), cases.is_tree(name), q, J, cases.gravity3(name), axes, want, fill, rc)
 
 
 def _tiled(name):
