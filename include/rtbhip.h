@@ -477,6 +477,43 @@ int rtbhip_opspace(rtbhip_dyn_t dyn, const double *q, const double *J, int64_t N
 int rtbhip_tree_opspace(rtbhip_tree_t tree, const double *q, const double *J, int64_t N, const double *gravity3 /* host; may be NULL when Gx is NULL */,
                         int32_t axes_mask, double *Mx, double *Gx, double *asada, void *stream);
 
+/* RESOLVED-RATE MOTION CONTROL -- the loop the reference's README opens with, `v, arrived = rtb.p_servo(panda.fkine(panda.q), Tep, 1);
+ * panda.qd = np.linalg.pinv(panda.jacobe(panda.q)) @ v`, in one launch, and iterated on the device.  Per row, for it = 0 .. steps - 1:
+ *     T, J = fkine(q), jacob(q)     method 1 "rpy": J = jacobe -- the error is seen from the end-effector frame, as in the README;
+ *                                   method 0 "angle-axis": J = jacob0 -- the error is in the base frame.  The pairing is part of the definition.
+ *     e    = the error of rtbhip_p_servo for that method, tools/p_servo.py:46-106
+ *     arr  = sum|e| < threshold     on e, before the gain (p_servo.py:104)
+ *     r    = gain6 * e - J qnull    qnull = 0 when not given
+ *     qd   = qnull + X r            X = pinv(J)
+ *     q    = q + dt * qd ;  its = it + 1 ;  if arr: stop -- the step of the iteration that arrives IS taken, as in the README loop
+ * steps = 1 is the single resolved-rate step: qd = pinv(J(q)) v, and arrived is for the incoming q.  X is applied as solves, never formed, by the
+ * rule of rtbhip_opspace: n = 6 with damping 0 by LU with partial pivoting; n > 6, or n = 6 with damping d > 0, J^T (J J^T + d^2 I)^-1 by an
+ * LDL^T; n < 6 (J^T J + d^2 I)^-1 J^T by an LDL^T of the n x n Gram matrix; exact divisions.  A row whose system has a zero or non-finite pivot
+ * (a singular J with damping 0, a non-finite q) is left non-finite and touches no other row: nothing is repaired, `damping` is the remedy
+ * (the policy of rtbhip_ik_vjp).  NOT REPRODUCED: numpy's SVD-truncated pinv at a rank-deficient J.  A non-finite row never arrives: it runs out
+ * its steps.  The chain's own last constant is the tool; there is no base.
+ * The ONE argument is a parameter block; `size` must be sizeof the block.  q (N, n), Tep (N, 4, 4) or one (4, 4) for all rows (nTep = 1), qnull
+ * (N, n) or NULL; outputs qd (N, n): the rate of the last iteration taken, q_out (N, n), arrived (N) bytes 0 / 1, its (N): iterations taken --
+ * either of qd / q_out may be NULL (not both), arrived and its may be NULL; a NULL output is not stored.  Every array is DEVICE memory, fp64; the
+ * launch goes to `stream` and reads no host memory after the call returns (a captured graph replays).  Chains of 1..10 joints with jindex
+ * 0..n-1.  N == 0 returns RTBHIP_OK without a launch.  RTBHIP_EINVAL: a NULL block or a wrong size, unknown chain handle, negative N, nTep
+ * neither N nor 1, a NULL input with N > 0, qd and q_out both NULL, a chain without joints, a chain whose jindex is not 0..n-1, a method that is
+ * not 0 or 1, a negative or non-finite damping, a non-finite gain6 / threshold / dt, steps below 1.  RTBHIP_ELIMIT: more than 10 joints, more
+ * than 4096 steps, a batch beyond one launch's tiles (2^31 - 1 tiles of 64 rows). */
+typedef struct rtbhip_rrmc_args {
+    uint32_t size;                    /* sizeof(rtbhip_rrmc_args) */
+    int32_t  method;                  /* 0 angle-axis / jacob0, 1 rpy / jacobe */
+    rtbhip_chain_t chain;
+    int64_t  N, nTep;                 /* nTep == N or 1 */
+    const double *q, *Tep, *qnull;    /* device; qnull may be NULL */
+    double   gain6[6], threshold, damping, dt;
+    int32_t  steps;                   /* 1..4096 */
+    double  *qd, *q_out;              /* device; either may be NULL, not both */
+    uint8_t *arrived; int32_t *its;   /* device; either may be NULL */
+    void    *stream;
+} rtbhip_rrmc_args;
+int rtbhip_rrmc(const rtbhip_rrmc_args *args);
+
 /* Mixed fleet (BASELINE config 5): n_chains independent chains, each with its own batch; one
  * launch walks all of them (block -> chain map).  q[c] is (N[c], q_width_c), T[c] (N[c],4,4),
  * J[c] (N[c],6,n_c).  The pointer tables themselves are HOST arrays. */

@@ -7,6 +7,7 @@
 #include "partial_device.h"
 #include "frames_device.h"
 #include "tree_device.h"
+#include "kin_reg.h"
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -667,6 +668,8 @@ __attribute__((weak)) int launch_tree_coriolis_vjp(const Tree *t, const DevGroup
 // ... and of the implicit-function adjoint of the inverse kinematics (ikgrad_kernels.hip), weak for the same reason
 __attribute__((weak)) int launch_ik_vjp(const Chain *c, const DevChain &dc, const double *q, int64_t N, const double *Tep, const int32_t *success,
                                         int rows, double d2, const double *gq, double *gTep, double *gtwist, hipStream_t s);
+// ... and of resolved-rate motion control (rrmc_kernels.hip), weak for the same reason
+__attribute__((weak)) int launch_rrmc(const Chain *c, const DevChain &dc, const rtbhip_rrmc_args *a, hipStream_t s);
 // ... and of the operational-space dynamics (opspace_kernels.hip, tree_opspace_kernels.hip), weak for the same reason
 __attribute__((weak)) int launch_opspace(const Dyn *d, const DevLink *links, const double *q, const double *J, int64_t N, const double *grav3, int axes,
                                          double *Mx, double *Gx, double *asada, hipStream_t s);
@@ -1345,6 +1348,40 @@ int rtbhip_ik_vjp(rtbhip_chain_t chain, const double *q, int64_t N, const double
     DevChain ops;
     RTB_TRY(chain_device_ops(c, &ops, nullptr));
     return launch_ik_vjp(c, ops, q, N, Tep, success, rows, damping * damping, gq, gTep, gtwist, (hipStream_t)stream);
+}
+
+/* resolved-rate motion control, one step or the servo loop on the device (k_rrmc): device pointers only, one parameter block */
+int rtbhip_rrmc(const rtbhip_rrmc_args *a)
+{
+    const char *fn = "rrmc";
+    RTB_TRACE(fn);
+    if (!a) return refuse(fn, "NULL parameter block");
+    if (a->size != sizeof(rtbhip_rrmc_args)) return refuse(fn, "size is not sizeof(rtbhip_rrmc_args): built against another header");
+    const std::shared_ptr<Chain> c_owner = chain_from_handle(a->chain);
+    Chain *c = c_owner.get();
+    if (!c) return refuse(fn, "unknown chain handle");
+    if (a->N < 0) return refuse(fn, "negative N");
+    if (a->nTep != a->N && a->nTep != 1) return refuse(fn, "nTep must be N or 1");
+    if (a->N > 0 && (!a->q || !a->Tep)) return refuse(fn, "NULL input with N > 0");
+    if (a->N > 0 && !a->qd && !a->q_out) return refuse(fn, "qd and q_out are both NULL: there is nothing to compute");
+    if (c->n < 1) return refuse(fn, "chain has no joints");
+    if (c->q_width != c->n) return refuse(fn, "chain must use jindex 0..n-1");
+    if (a->method != 0 && a->method != 1) return refuse(fn, "method must be 0 angle-axis or 1 rpy");
+    if (!(a->damping >= 0.0) || !std::isfinite(a->damping)) return refuse(fn, "damping must be finite and >= 0");
+    bool finite = std::isfinite(a->threshold) && std::isfinite(a->dt);
+    for (int k = 0; k < 6; ++k) finite = finite && std::isfinite(a->gain6[k]);
+    if (!finite) return refuse(fn, "gain6, threshold and dt must be finite");
+    if (a->steps < 1) return refuse(fn, "steps must be at least 1");
+    if (c->n > kKinRegMax) return refuse(fn, "chains of 1..10 joints", RTBHIP_ELIMIT);
+    if (a->steps > 4096) return refuse(fn, "at most 4096 steps", RTBHIP_ELIMIT);
+    if ((a->N + 63) / 64 > 0x7fffffff) return refuse(fn, "batch too large for one launch", RTBHIP_ELIMIT);
+    if (a->N == 0) return RTBHIP_OK;
+    if (!launch_rrmc) return refuse(fn, "not built into this library");
+    DeviceScope dscope;
+    RTB_TRY(dscope.enter_for(fn, a->q));
+    DevChain ops;
+    RTB_TRY(chain_device_ops(c, &ops, nullptr));
+    return launch_rrmc(c, ops, a, (hipStream_t)a->stream);
 }
 
 int rtbhip_ik_restart(rtbhip_chain_t chain, uint64_t seed, int64_t target, int32_t search, double *q_n)

@@ -9,6 +9,7 @@ Only the hot path named in BASELINE.json / SURVEY.md section 8 is here:
   urdf / xacro        URDF loader + the reference's URDF -> ETS lowering; xacro expander (stdlib only); 20 pre-expanded robot descriptions
   angle_axis / p_servo / hessian_from_jacobian    the exports of the extension module that take finished matrices
   opspace             inertia_x, gravload_x and Asada's manipulability measure of a DHRobot / ERobot: one fused launch each
+  servo               rrmc: p_servo + pinv(J) as one fused launch; servo: the resolved-rate loop iterated on the device
   compat.fknm / compat.frne   plug-in modules with the reference extension modules' own function tables
   fleet_fkine_jacob   many different chains in one call;  ShardedBatch / shard_range  one row block per GPU rank
 All arithmetic runs in hand-written HIP kernels (../csrc) behind the C ABI of include/rtbhip.h; there is no
@@ -27,6 +28,7 @@ from . import urdf  # noqa: F401
 from . import xacro  # noqa: F401
 from . import jit  # noqa: F401
 from . import opspace  # noqa: F401
+from . import servo  # noqa: F401
 from .fleet import fleet_fkine_jacob, fleet_fkine_jacob_packed  # noqa: F401
 from .shard import ShardedBatch, Communicator  # noqa: F401
 
