@@ -514,6 +514,56 @@ typedef struct rtbhip_rrmc_args {
 } rtbhip_rrmc_args;
 int rtbhip_rrmc(const rtbhip_rrmc_args *args);
 
+/* REACTIVE QP SERVO -- the manipulability-maximising motion controller of the reference's examples/mmc.py (Haviland & Corke, "A purely-reactive
+ * manipulability-maximising motion controller") with Robot.joint_velocity_damper's rows (robot/Robot.py:1413-1419) and the joint-velocity box as
+ * its constraints, in one launch, and iterated on the device.  Per row, for it = 0 .. steps - 1:
+ *     T, J0 = fkine(q), jacob0(q)   J = jacobe(q) for method 1 "rpy", J0 for method 0 "angle-axis": the pairing of rtbhip_rrmc
+ *     e    = the error of rtbhip_p_servo for that method ;  s = sum|e| ;  arr = s < threshold, on e, before the gain
+ *     v    = gain6 * e
+ *     qd   = argmin over (qd, delta) of  1/2 Y |qd|^2 + 1/2 (ks / s) |delta|^2 - (1 / km) jacobm(q)^T qd
+ *              subject to  J qd + delta = v,  lo <= qd <= hi
+ *     q    = q + dt * qd ;  its = it + 1 ;  if arr: stop -- the step of the iteration that arrives IS taken, as in rtbhip_rrmc
+ * jacobm is what rtbhip_jacobm returns for all six axes (Yoshikawa's measure of J0); km = 0 leaves the linear term out.  The box is
+ * [-qdlim_j, +qdlim_j] (none when qdlim is NULL), tightened by the dampers:
+ *     qlim_hi_j - q_j <= pi:   hi_j = min(hi_j,  damper_gain ((qlim_hi_j - q_j) - ps) / (pi - ps))
+ *     q_j - qlim_lo_j <= pi:   lo_j = max(lo_j, -damper_gain ((q_j - qlim_lo_j) - ps) / (pi - ps))
+ * A limit of + / - infinity has no damper.  With the slack eliminated this is a strictly convex QP in qd, solved per row by an active-set
+ * iteration on the 6 x 6 system (J_F J_F^T + (Y s / ks) I) -- one change of the held set per round, at most 3 n + 2 rounds.
+ * DEVIATIONS from the reference: both sides of a joint are applied independently (the reference has one row per joint and lets one side override
+ * the other; the two agree whenever pi is at most half the joint's range); the slack's weight is ks / sum|e| of p_servo's own error as in
+ * IK_QP.step (the example's 1 / e carries a unit slip in its rpy part); the example's box of 10 on the slack is not imposed, bit 1 of status
+ * reports an iteration whose |v - J qd|inf exceeded it.
+ * UNSOLVABLE rows -- an empty box (lo_j > hi_j), rounds that run out, a q, an error or a solve that is not finite -- have bit 0 of status set
+ * and qd / q_out non-finite; such a row never arrives, runs out its steps and touches no other row.  A joint inside ps of ONE limit does not
+ * empty the box: it only makes that side's bound cross zero (the joint must retreat).  The box is empty when that bound crosses the other side's:
+ * a joint past its limit by more than ps + qdlim_j (pi - ps) / damper_gain, or a joint within ps of both of its limits.
+ * Nothing is repaired (the policy of rtbhip_rrmc).
+ * The ONE argument is a parameter block; `size` must be sizeof the block.  q (N, n), Tep (N, 4, 4) or one (4, 4) for all rows (nTep = 1):
+ * DEVICE memory.  qlim (2, n): lower limits then upper, and qdlim (n) or NULL: HOST memory, copied into the launch's parameters before the call
+ * returns (a captured graph replays them).  Outputs, DEVICE memory: qd (N, n): the rate of the last iteration taken, q_out (N, n), arrived (N)
+ * bytes 0 / 1, its (N): iterations taken, status (N) bytes -- either of qd / q_out may be NULL (not both), arrived, its and status may be NULL;
+ * a NULL output is not stored.  fp64; the launch goes to `stream`.  Chains of 6..10 joints with jindex 0..n-1 (jacobm needs a square or
+ * redundant arm).  N == 0 returns RTBHIP_OK without a launch.  RTBHIP_EINVAL: a NULL block or a wrong size, unknown chain handle, negative N,
+ * nTep neither N nor 1, a NULL input with N > 0, qd and q_out both NULL, a chain whose jindex is not 0..n-1, a method that is not 0 or 1,
+ * a Y or ks that is not positive, a negative km, a negative ps, a pi that is not above ps, a non-finite scalar, a NaN in qlim or qdlim,
+ * a negative qdlim, steps below 1.  RTBHIP_ELIMIT: fewer than 6 or more than 10 joints, more than 4096 steps, a batch beyond one
+ * launch's tiles (2^31 - 1 tiles of 64 rows). */
+typedef struct rtbhip_mmc_args {
+    uint32_t size;                    /* sizeof(rtbhip_mmc_args) */
+    int32_t  method;                  /* 0 angle-axis / jacob0, 1 rpy / jacobe */
+    rtbhip_chain_t chain;
+    int64_t  N, nTep;                 /* nTep == N or 1 */
+    const double *q, *Tep;            /* device */
+    const double *qlim, *qdlim;       /* HOST: (2, n) and (n); qdlim may be NULL */
+    double   gain6[6], threshold, dt;
+    int32_t  steps;                   /* 1..4096 */
+    double   Y, ks, km, ps, pi, damper_gain;
+    double  *qd, *q_out;              /* device; either may be NULL, not both */
+    uint8_t *arrived; int32_t *its; uint8_t *status;   /* device; each may be NULL */
+    void    *stream;
+} rtbhip_mmc_args;
+int rtbhip_mmc(const rtbhip_mmc_args *args);
+
 /* Mixed fleet (BASELINE config 5): n_chains independent chains, each with its own batch; one
  * launch walks all of them (block -> chain map).  q[c] is (N[c], q_width_c), T[c] (N[c],4,4),
  * J[c] (N[c],6,n_c).  The pointer tables themselves are HOST arrays. */

@@ -670,6 +670,8 @@ __attribute__((weak)) int launch_ik_vjp(const Chain *c, const DevChain &dc, cons
                                         int rows, double d2, const double *gq, double *gTep, double *gtwist, hipStream_t s);
 // ... and of resolved-rate motion control (rrmc_kernels.hip), weak for the same reason
 __attribute__((weak)) int launch_rrmc(const Chain *c, const DevChain &dc, const rtbhip_rrmc_args *a, hipStream_t s);
+// ... and of the reactive QP servo (mmc_kernels.hip), weak for the same reason
+__attribute__((weak)) int launch_mmc(const Chain *c, const DevChain &dc, const rtbhip_mmc_args *a, hipStream_t s);
 // ... and of the operational-space dynamics (opspace_kernels.hip, tree_opspace_kernels.hip), weak for the same reason
 __attribute__((weak)) int launch_opspace(const Dyn *d, const DevLink *links, const double *q, const double *J, int64_t N, const double *grav3, int axes,
                                          double *Mx, double *Gx, double *asada, hipStream_t s);
@@ -1382,6 +1384,47 @@ int rtbhip_rrmc(const rtbhip_rrmc_args *a)
     DevChain ops;
     RTB_TRY(chain_device_ops(c, &ops, nullptr));
     return launch_rrmc(c, ops, a, (hipStream_t)a->stream);
+}
+
+/* the reactive QP servo, one step or the loop on the device (k_mmc): one parameter block; q, Tep and the outputs on the device, qlim / qdlim on the host */
+int rtbhip_mmc(const rtbhip_mmc_args *a)
+{
+    const char *fn = "mmc";
+    RTB_TRACE(fn);
+    if (!a) return refuse(fn, "NULL parameter block");
+    if (a->size != sizeof(rtbhip_mmc_args)) return refuse(fn, "size is not sizeof(rtbhip_mmc_args): built against another header");
+    const std::shared_ptr<Chain> c_owner = chain_from_handle(a->chain);
+    Chain *c = c_owner.get();
+    if (!c) return refuse(fn, "unknown chain handle");
+    if (a->N < 0) return refuse(fn, "negative N");
+    if (a->nTep != a->N && a->nTep != 1) return refuse(fn, "nTep must be N or 1");
+    if (a->N > 0 && (!a->q || !a->Tep || !a->qlim)) return refuse(fn, "NULL input with N > 0");
+    if (a->N > 0 && !a->qd && !a->q_out) return refuse(fn, "qd and q_out are both NULL: there is nothing to compute");
+    if (c->q_width != c->n) return refuse(fn, "chain must use jindex 0..n-1");
+    if (a->method != 0 && a->method != 1) return refuse(fn, "method must be 0 angle-axis or 1 rpy");
+    bool finite = std::isfinite(a->threshold) && std::isfinite(a->dt) && std::isfinite(a->Y) && std::isfinite(a->ks) && std::isfinite(a->km) &&
+                  std::isfinite(a->ps) && std::isfinite(a->pi) && std::isfinite(a->damper_gain);
+    for (int k = 0; k < 6; ++k) finite = finite && std::isfinite(a->gain6[k]);
+    if (!finite) return refuse(fn, "gain6, threshold, dt, Y, ks, km, ps, pi and damper_gain must be finite");
+    if (!(a->Y > 0.0) || !(a->ks > 0.0)) return refuse(fn, "Y and ks must be positive (the QP must be strictly convex)");
+    if (a->km < 0.0) return refuse(fn, "km must be >= 0");
+    if (a->ps < 0.0) return refuse(fn, "ps must be >= 0");
+    if (!(a->pi > a->ps)) return refuse(fn, "pi must be above ps");
+    if (a->steps < 1) return refuse(fn, "steps must be at least 1");
+    if (c->n < 6 || c->n > kKinRegMax) return refuse(fn, "chains of 6..10 joints", RTBHIP_ELIMIT);
+    if (a->steps > 4096) return refuse(fn, "at most 4096 steps", RTBHIP_ELIMIT);
+    if (a->N / 64 + (a->N % 64 != 0) > 0x7fffffff) return refuse(fn, "batch too large for one launch", RTBHIP_ELIMIT);   // (no N + 63: it overflows)
+    if (a->N == 0) return RTBHIP_OK;
+    for (int j = 0; j < c->n; ++j) {             // host arrays, read now (and once more by the launcher, into the launch's parameters)
+        if (std::isnan(a->qlim[j]) || std::isnan(a->qlim[c->n + j]) || (a->qdlim && std::isnan(a->qdlim[j]))) return refuse(fn, "NaN in qlim or qdlim");
+        if (a->qdlim && a->qdlim[j] < 0.0) return refuse(fn, "qdlim must be >= 0");
+    }
+    if (!launch_mmc) return refuse(fn, "not built into this library");
+    DeviceScope dscope;
+    RTB_TRY(dscope.enter_for(fn, a->q));
+    DevChain ops;
+    RTB_TRY(chain_device_ops(c, &ops, nullptr));
+    return launch_mmc(c, ops, a, (hipStream_t)a->stream);
 }
 
 int rtbhip_ik_restart(rtbhip_chain_t chain, uint64_t seed, int64_t target, int32_t search, double *q_n)

@@ -46,6 +46,16 @@ class rtbhip_rrmc_args(C.Structure):
                 ("qd", C.c_void_p), ("q_out", C.c_void_p), ("arrived", C.c_void_p), ("its", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class rtbhip_mmc_args(C.Structure):
+    """the parameter block of rtbhip_mmc (include/rtbhip.h), field for field; qlim and qdlim are HOST addresses"""
+    _fields_ = [("size", C.c_uint32), ("method", C.c_int32), ("chain", C.c_uint64), ("N", C.c_int64), ("nTep", C.c_int64),
+                ("q", C.c_void_p), ("Tep", C.c_void_p), ("qlim", C.c_void_p), ("qdlim", C.c_void_p),
+                ("gain6", C.c_double * 6), ("threshold", C.c_double), ("dt", C.c_double), ("steps", C.c_int32),
+                ("Y", C.c_double), ("ks", C.c_double), ("km", C.c_double), ("ps", C.c_double), ("pi", C.c_double), ("damper_gain", C.c_double),
+                ("qd", C.c_void_p), ("q_out", C.c_void_p), ("arrived", C.c_void_p), ("its", C.c_void_p), ("status", C.c_void_p),
+                ("stream", C.c_void_p)]
+
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _vp = C.c_void_p
@@ -169,6 +179,7 @@ SIGNATURES = {
     "rtbhip_opspace": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "rtbhip_tree_opspace": (C.c_int, [_u64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "rtbhip_rrmc": (C.c_int, [C.POINTER(rtbhip_rrmc_args)]),
+    "rtbhip_mmc": (C.c_int, [C.POINTER(rtbhip_mmc_args)]),
     "rtbhip_fleet_fkine_jacob": (C.c_int, [C.POINTER(_u64), _i32, C.POINTER(_vp), C.POINTER(_i64), _i32,
                                            C.POINTER(_vp), C.POINTER(_vp), _i32, _vp]),
     "rtbhip_fleet_fkine_jacob_packed": (C.c_int, [C.POINTER(_u64), _i32, C.POINTER(_vp), C.POINTER(_i64), _i32, C.POINTER(_vp), _i32, _vp]),
